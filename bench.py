@@ -13,6 +13,11 @@ bench.py --gpus N`` does the same through the launcher.  Each rank runs one inde
 (replicas; no collective on the data path); a gloo group is used only for the
 start barrier and the max-over-ranks timing.
 
+A plain run sets up, warms up, times ``--steps`` gradient steps and prints the line (``ms_per_step``: wall
+milliseconds per timed step).  ``--full`` adds the torch-CPU oracle baseline of the same workload
+(``cpu_baseline``); ``--dump-outputs DIR`` writes what the timed steps left as ``DIR/<name>.npy``
+(dump_outputs).
+
 Prints ONE JSON line on rank 0.
 """
 
@@ -423,6 +428,40 @@ ENGINE_TIMERS = {1: "host wall, first AQL doorbell to completion signal", 0: "HI
                  2: "HIP events on the engine stream"}
 
 
+INFO_COLS = {"td7": 3, "td3": 3, "sac": 6}  # the agent's info keys (rle.h: the other columns of a row are unused)
+INFO_RING = 4096                            # rows the engine's device info ring keeps (rle_get_info)
+
+
+def dump_outputs(out_dir, eng, rep, nets, algo, steps, lap, rank=0):
+    """--dump-outputs: what the timed rle_step_timed(steps) left, i.e. what a caller of the training step gets
+    back from the engine, as <out_dir>/<name>.npy (float32; about 16 MB for the headline config).  Seeds, fill
+    and weights are fixed by the arguments, so two builds run with the same arguments can be compared file by file:
+      info                the info rows of the last min(steps, 4096) timed steps, the agent's columns (losses;
+                          None entries, NaN in the C ABI, are written as 0)
+      indices             replay rows of the last step's batch
+      priority            LAP priorities of the whole replay after the last step's update (TD7)
+      value_bounds        TD7's running target-value bounds
+      param.<net>.<name>  every tensor of every net after the last step's updates
+    Ranks other than 0 write rank<r>.<name>.npy (their own seed)."""
+    os.makedirs(out_dir, exist_ok=True)
+    pre = "" if rank == 0 else f"rank{rank}."
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, f"{pre}{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+    if steps > 0:
+        rows = eng.get_info((steps - 1) % INFO_RING + 1)[:, :INFO_COLS[algo]]
+        save("info", np.where(np.isnan(rows), np.float32(0), rows))
+        save("indices", eng.last_indices())
+    if lap:
+        save("priority", rep.get_priority())
+    if algo == "td7":
+        save("value_bounds", eng.value_bounds())
+    for net, params in nets.items():
+        for name, v in params.items():
+            save(f"param.{net}.{name}", eng.get_param(net, name, v.shape))
+
+
 def multi_seed(args, K, world, rank, local, dist, algo_id, lap, E, init_agent, cuda_sync, chunk=25):
     """K independent seeds per GPU: K engines, each with its own replay,
     weights, Philox stream and HIP stream, stepped round-robin in chunks without host syncs.
@@ -674,7 +713,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the torch-CPU oracle baseline of the same "
+                         "workload (cpu_baseline in the JSON line); a plain run only sets up, warms up and times")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they left to DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-replay", type=int, default=N_REPLAY,
                     help="replay rows of the CPU baseline's oracle (default the GPU run's 1M; tests use fewer)")
@@ -689,6 +733,9 @@ def main():
     args = ap.parse_args()
     if (args.algo, args.env, args.batch) not in WORK:
         ap.error(f"no SURVEY §8(d) work figures for {args.algo} {args.env} B={args.batch}")
+    if args.dump_outputs and args.seeds_per_gpu > 1:
+        ap.error("--dump-outputs writes the single engine's state: not with --seeds-per-gpu > 1")
+    cpu_base = args.full and not args.no_cpu_baseline
     lap = args.algo == "td7"  # TD7 runs LAP (td7_exp.sh); SAC / TD3 the uniform replay
     stub = _stub_engine_module(os.environ["RLE_BENCH_STUB"]) if os.environ.get("RLE_BENCH_STUB") else None
 
@@ -740,7 +787,8 @@ def main():
         return multi_seed(args, K, world, rank, local, dist, algo_id, lap, E, init_agent, cuda_sync)
     cfg = E.make_config(algo_id, s_dim, a_dim, H, args.batch, use_lap=lap, seed=111 * (rank + 1), device=local)
     eng = E.Engine(cfg, E.parse_plan(args.plan))
-    for net, params in init_agent(args.algo, s_dim, a_dim, H, 123 + rank).items():
+    nets = init_agent(args.algo, s_dim, a_dim, H, 123 + rank)
+    for net, params in nets.items():
         for name, v in params.items():
             eng.set_param(net, name, v)
     rep = E.Replay(N_REPLAY, s_dim, a_dim, lap, device=local)
@@ -762,9 +810,11 @@ def main():
     launches = (eng.launch_count() - n_l0) / args.steps
     wall = t1 - t0
     wall, gpu_s = max_over_ranks([wall, gpu_ms / 1e3], dist)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, rep, nets, args.algo, args.steps, lap, rank)
 
     cb = None
-    if world > 1 and not args.no_cpu_baseline:  # (every rank: the N concurrent CPU processes)
+    if world > 1 and cpu_base:  # (every rank: the N concurrent CPU processes)
         cb = cpu_baseline_ranks(dist, rank, world, pin_cpus, args.cpu_seconds, args.algo, args.env, args.batch, lap,
                                 args.cpu_replay)
     pins = [None] * world
@@ -783,7 +833,7 @@ def main():
     out["host_thread_busy_frac"] = round((c1 - c0) / max(wall, 1e-9), 4)
     if world > 1:
         out["config"]["rank_pinning"] = pins
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and cpu_base:
         out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, args.algo, args.env, args.batch, lap,
                                            n_replay=args.cpu_replay)
     elif cb is not None:

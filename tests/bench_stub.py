@@ -3,6 +3,8 @@ JSON line without a GPU (RLE_BENCH_STUB=<this file>).  Test infrastructure only.
 
 import time
 
+import numpy as np
+
 RLE_TD7, RLE_TD3, RLE_SAC = 0, 1, 2
 
 
@@ -19,7 +21,7 @@ def make_config(algo, s, a, h, b, **kw):
 
 
 def init_agent(algo, s, a, h, seed):
-    return {}
+    return {"policy": {"l0.weight": np.zeros((2, 3), np.float32), "l0.bias": np.zeros(2, np.float32)}}
 
 
 def parse_plan(text):
@@ -32,6 +34,9 @@ class Replay:
 
     def fill_random(self, n, seed=0):
         pass
+
+    def get_priority(self):
+        return np.ones(64, np.float32)
 
 
 class Engine:
@@ -64,3 +69,18 @@ class Engine:
 
     def synchronize(self):
         pass
+
+    # what --dump-outputs reads back: rows numbered by the step they belong to, None (NaN) in the last column
+    def get_info(self, n):
+        rows = np.full((n, 8), np.nan, np.float32)
+        rows[:, :2] = np.arange(self.n - n + 1, self.n + 1, dtype=np.float32)[:, None]
+        return rows
+
+    def last_indices(self):
+        return np.arange(self.cfg["b"], dtype=np.int64) + self.n
+
+    def value_bounds(self):
+        return np.array([0, 0, -1e8, 1e8], np.float32)
+
+    def get_param(self, net, name, shape=None):
+        return np.full(shape, self.n, np.float32)

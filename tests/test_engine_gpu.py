@@ -716,6 +716,57 @@ def test_bench_program_1m_lap_replay_matches_oracle():
             assert_params_close(got, ref, tol, (net, name))
 
 
+def test_bench_dump_outputs_are_the_timed_steps_state(tmp_path):
+    """``bench.py --gpus 1 --steps 13 --warmup 5 --dump-outputs DIR`` (a plain run: no CPU baseline in its line)
+    writes what its 13 timed steps left: bit for bit the info rows, last batch indices, all 1M priorities, value
+    bounds and every parameter of an engine set up here with bench.py's seeds and stepped 5 + 13 times."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import bench
+    from conftest import REPO
+    from rl.nn.layout import init_agent
+
+    steps, warmup = 13, 5
+    res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                          "--warmup", str(warmup), "--dump-outputs", str(tmp_path)], capture_output=True, text=True,
+                         timeout=120)
+    assert res.returncode == 0, res.stderr[-2000:]
+    out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == steps and out["ms_per_step"] > 0 and "cpu_baseline" not in out
+    got = {f.name[:-len(".npy")]: np.load(f) for f in tmp_path.iterdir()}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+
+    S, A, Hd, B, N = bench.S, bench.A, bench.H, bench.B, bench.N_REPLAY
+    eng = E.Engine(E.make_config(E.RLE_TD7, S, A, Hd, B, use_lap=True, seed=111), E.parse_plan(""))
+    nets = init_agent("td7", S, A, Hd, 123)
+    for net, params in nets.items():
+        for name, v in params.items():
+            eng.set_param(net, name, v)
+    rep = E.Replay(N, S, A, True)
+    rep.fill_random(N, seed=0)
+    eng.bind(rep)
+    eng.step_timed(warmup)
+    eng.step_timed(steps)
+    info = eng.get_info(steps)[:, :3]
+    assert np.isnan(info[:, 2]).any() and np.isfinite(info[:, :2]).all()  # (train/policy is None every 2nd step)
+    np.testing.assert_array_equal(got.pop("info"), np.where(np.isnan(info), np.float32(0), info))
+    np.testing.assert_array_equal(got.pop("indices"), eng.last_indices().astype(np.float32))
+    np.testing.assert_array_equal(got.pop("priority"), rep.get_priority())
+    np.testing.assert_array_equal(got.pop("value_bounds"), eng.value_bounds())
+    for net, params in nets.items():
+        for name, v in params.items():
+            g = got.pop(f"param.{net}.{name}")
+            assert g.shape == v.shape
+            if net in ("encoder", "policy", "q1", "q2"):
+                assert not np.array_equal(g, v), f"{net}.{name} was never trained"
+            np.testing.assert_array_equal(g, eng.get_param(net, name, v.shape), err_msg=f"{net}.{name}")
+    assert not got
+
+
 def _wide_run(B, n, plan, env="Humanoid-v4"):
     g = _synthetic_golden("td7", env, 256, B, 8192, 8192, n, True, 95)
     eng, rep, tp = engine_from_golden(g, plan=plan)

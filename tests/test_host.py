@@ -226,8 +226,8 @@ def test_bench_gpus_n_launches_its_own_ranks():
     env = dict(os.environ, RLE_BENCH_STUB=os.path.join(REPO, "tests", "bench_stub.py"))
     env.pop("WORLD_SIZE", None)
     res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "40",
-                          "--warmup", "2", "--cpu-seconds", "0.5", "--cpu-replay", "8192"], capture_output=True,
-                         text=True, timeout=240, env=env)
+                          "--warmup", "2", "--full", "--cpu-seconds", "0.5", "--cpu-replay", "8192"],
+                         capture_output=True, text=True, timeout=240, env=env)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, res.stdout
@@ -293,6 +293,47 @@ def test_bench_seeds_per_gpu_line():
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["config"]["seeds_per_gpu"] == 2 and "one HIP stream each" in out["config"]["parallelism"]
     assert out["value"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain ``bench.py --gpus 1 --steps N --warmup W`` (stub engine) runs no CPU baseline (that is ``--full``),
+    times exactly N steps, reports ms_per_step, and ``--dump-outputs`` writes the last step's arrays as float32
+    .npy files: the same files from a second run with the same arguments."""
+    env = dict(os.environ, RLE_BENCH_STUB=os.path.join(REPO, "tests", "bench_stub.py"))
+    env.pop("WORLD_SIZE", None)
+    dumps = []
+    for d in ("a", "b"):
+        res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "40",
+                              "--warmup", "3", "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True,
+                             timeout=120, env=env)
+        assert res.returncode == 0, res.stderr[-2000:]
+        out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+        assert "cpu_baseline" not in out
+        assert out["steps"] == 40 and out["warmup"] == 3 and out["unit"] == "gradient-steps/s"
+        assert out["higher_is_better"] is True and out["dtype"] == "fp32"
+        assert abs(out["ms_per_step"] * out["value"] - 1e3) < 1.0  # one GPU: value = 1000 / ms_per_step
+        dumps.append({f.name[:-len(".npy")]: np.load(f) for f in sorted((tmp_path / d).iterdir())})
+    a, b = dumps
+    assert sorted(a) == ["indices", "info", "param.policy.l0.bias", "param.policy.l0.weight", "priority",
+                         "value_bounds"]
+    assert all(v.dtype == np.float32 for v in a.values())
+    # the stub numbers its rows by step: the 40 timed steps after 3 warm-up steps, None written as 0
+    assert a["info"].shape == (40, 3) and a["info"][-1].tolist() == [43.0, 43.0, 0.0] and a["info"][0, 0] == 4.0
+    assert a["indices"][0] == 43 and a["param.policy.l0.weight"].shape == (2, 3)
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k])
+
+
+def test_bench_full_adds_cpu_baseline():
+    """``--full`` keeps what the plain run dropped: the torch-CPU oracle baseline of the same workload."""
+    env = dict(os.environ, RLE_BENCH_STUB=os.path.join(REPO, "tests", "bench_stub.py"))
+    env.pop("WORLD_SIZE", None)
+    res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "40",
+                          "--warmup", "2", "--full", "--cpu-seconds", "0.5", "--cpu-replay", "8192"],
+                         capture_output=True, text=True, timeout=240, env=env)
+    assert res.returncode == 0, res.stderr[-2000:]
+    out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["cpu_baseline"]["value"] > 0 and out["cpu_baseline"]["kind"] == "port"
 
 
 def test_bench_gpus_more_than_visible_fails():

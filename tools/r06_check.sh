@@ -11,7 +11,7 @@ cd $ROOT
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > $OUT/${TAG}_gpu_tests.txt 2>&1 \
   || { echo "GPU TESTS FAILED"; tail -40 $OUT/${TAG}_gpu_tests.txt; exit 1; }
 tail -1 $OUT/${TAG}_gpu_tests.txt
-timeout -k 10 300 python bench.py --steps 2000 --warmup 50 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err \
+timeout -k 10 300 python bench.py --full --steps 2000 --warmup 50 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err \
   || { echo BENCH FAILED; tail -20 $OUT/${TAG}_bench.err; exit 1; }
 cat $OUT/${TAG}_bench.json
 timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/${TAG}_driver_cmd.json 2>&1 \

@@ -47,7 +47,7 @@ if [ $PART = main ]; then
   # (the bench lines below cite this round's PMC and sampler files)
   cp $OUT/r06_pmc.json $OUT/r06_sampler.csv $OUT/r06_sampler_pmc.json profiles/ || exit 1
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/r06_smoke.txt 2>&1 || { echo SMOKE FAILED; tail -20 $OUT/r06_smoke.txt; exit 1; }
-  timeout -k 10 300 python bench.py --steps 2000 --warmup 50 > $OUT/r06_bench.json 2> $OUT/r06_bench.err || { echo BENCH FAILED; tail -20 $OUT/r06_bench.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 2000 --warmup 50 > $OUT/r06_bench.json 2> $OUT/r06_bench.err || { echo BENCH FAILED; tail -20 $OUT/r06_bench.err; exit 1; }
   cat $OUT/r06_bench.json
   : > $OUT/r06_driver_cmd.jsonl
   for i in 1 2 3; do
@@ -66,7 +66,7 @@ else
   : > $OUT/r06_secondary_configs.jsonl
   for cfg in "b1024:--batch 1024" "ant:--env Ant-v4" "sac:--algo sac" "td3:--algo td3 --env HalfCheetah-v4"; do
     tag=${cfg%%:*}; args=${cfg#*:}
-    timeout -k 10 300 python bench.py --steps 2000 --warmup 50 $args >> $OUT/r06_secondary_configs.jsonl 2> $OUT/r06_sec_$tag.err \
+    timeout -k 10 300 python bench.py --full --steps 2000 --warmup 50 $args >> $OUT/r06_secondary_configs.jsonl 2> $OUT/r06_sec_$tag.err \
       || { echo "FAILED: $args"; tail -5 $OUT/r06_sec_$tag.err; exit 1; }
     prof_run $tag --steps 1000 --warmup 50 $args || exit 1
     echo "done $tag"

@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd $ROOT
 : > $OUT/secondary.jsonl
 for args in "--env Ant-v4" "--algo sac" "--algo td3 --env HalfCheetah-v4" "--batch 1024"; do
-  timeout -k 10 300 python bench.py --steps 2000 --warmup 50 $args >> $OUT/secondary.jsonl 2> $OUT/secondary.err || { echo "FAILED: $args"; tail -5 $OUT/secondary.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 2000 --warmup 50 $args >> $OUT/secondary.jsonl 2> $OUT/secondary.err || { echo "FAILED: $args"; tail -5 $OUT/secondary.err; exit 1; }
   echo "done $args"
 done
 : > $OUT/multiseed.jsonl
