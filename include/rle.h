@@ -158,6 +158,27 @@ int rle_replay_reset_max_priority(rle_replay* r);
 /* Gather rows (state, action, reward, next_state, notdone) for indices (lap.py:55-60). */
 int rle_replay_gather(rle_replay* r, int n, const long long* ind, float* state, float* action,
                       float* reward, float* next_state, float* notdone);
+/* Whole-replay state.  The reference's replays are NumPy arrays and Python scalars (lap.py:18-29,
+ * simple.py:15-27), so pickle.dumps(replay) and copy.deepcopy(replay) work on them as they are, as
+ * deepcopy(agent) does on the agent (run_w_checkpoint.py:72).  These entries give the HBM ring the same. */
+/* Rows per internal staging chunk of export / import / gather (no GPU call). */
+int rle_replay_io_rows(void);
+/* The arrays of lap.py:18-28 / simple.py:15-26 for slots first .. first+count-1 -> host, unpadded fp32
+ * (state [count][S], action [count][A], reward, next_state, notdone, priority [count]); any pointer may be
+ * NULL; priority: LAP replays only.  A host read: waits for the bound engines' enqueued steps. */
+int rle_replay_export(rle_replay* r, long long first, long long count, float* state, float* action,
+                      float* reward, float* next_state, float* notdone, float* priority);
+/* The reverse (unpickling those arrays): host -> slots first .. first+count-1.  Moves neither ptr nor size;
+ * a NULL priority leaves the priorities alone; the LAP sums follow in rle_replay_set_state. */
+int rle_replay_import(rle_replay* r, long long first, long long count, const float* state,
+                      const float* action, const float* reward, const float* next_state,
+                      const float* notdone, const float* priority);
+/* ptr, size, max_priority (lap.py:18-19,29) after an import: recomputes the LAP block and sub-block sums
+ * (rows at or past size count as 0) and makes bound engines redraw their prefetched batch. */
+int rle_replay_set_state(rle_replay* r, long long ptr, long long size, float max_priority);
+/* copy.deepcopy(replay) on the device(s): the whole ring, priorities, LAP sums, ptr / size / max_priority of
+ * src into dst (same capacity, dims and lap; the two may live on different GPUs).  No host round trip. */
+int rle_replay_copy(rle_replay* dst, rle_replay* src);
 
 /* ---- agent: rl/agent/{td7,td3,sac}.py ------------------------------------- */
 

@@ -50,6 +50,8 @@ hipError_t launch_act_chain(const ActChainArgs& a, hipStream_t st);
 hipError_t launch_fill(float* state, float* next_state, float* action, float* reward, float* notdone,
                        float* priority, long long n, int S, int Sp, int A, int Ap, unsigned long long seed,
                        hipStream_t st);
+hipError_t launch_replay_pack(const ReplayPackArgs& a, hipStream_t st);
+hipError_t launch_replay_unpack(const ReplayPackArgs& a, hipStream_t st);
 
 static thread_local std::string g_err;
 
@@ -219,6 +221,26 @@ struct Replay {
   // enqueued step: replay operations on `stream` wait for them first (an append after
   // rle_step_async must not race the step's priority scatter and block sums)
   std::vector<std::pair<Engine*, hipEvent_t>> users;
+  // export / import staging (allocated at the first rle_replay_export / _import): two device images and two
+  // pinned host images of kIoRows packed rows, the copies on a stream of their own so that the pack kernel of
+  // chunk k+1 (on `stream`) runs under the copy of chunk k
+  static constexpr long long kIoRows = 8192;
+  PinMem pin;
+  float* io_dev[2] = {nullptr, nullptr};
+  float* io_host[2] = {nullptr, nullptr};
+  hipStream_t io_stream = nullptr;
+  hipEvent_t io_kernel_ev[2] = {nullptr, nullptr}, io_copy_ev[2] = {nullptr, nullptr};
+  float* gather_host = nullptr;  // pinned image of a gather (grown on demand)
+  size_t gather_host_floats = 0;
+  size_t row_floats() const { return 2 * (size_t)S + A + 3; }
+  void io_init();
+  ReplayPackArgs pack_args() const {
+    ReplayPackArgs a{};
+    a.state = state, a.next_state = next_state, a.action = action;
+    a.reward = reward, a.notdone = notdone, a.priority = priority;
+    a.cap = cap, a.S = S, a.Sp = Sp, a.A = A, a.Ap = Ap;
+    return a;
+  }
   void wait_users();   // (after Engine: also drains the users' direct-dispatch bursts)
   void drain_users();  // the users' rle_step_async bursts on their own queues retired (host wait)
 };
@@ -4577,6 +4599,47 @@ void Replay::wait_users() {
   drain_users();
   for (auto& u : users) HIPCHK(hipStreamWaitEvent(stream, u.second, 0));
 }
+void Replay::io_init() {
+  if (io_stream) return;
+  const size_t n = (size_t)std::min(kIoRows, cap) * row_floats();  // (a chunk never has more rows than the ring)
+  for (int b = 0; b < 2; ++b) {
+    if (!io_dev[b]) io_dev[b] = mem.make<float>(n);
+    if (!io_host[b]) io_host[b] = static_cast<float*>(pin.alloc(n * sizeof(float)));
+    if (!io_kernel_ev[b]) HIPCHK(hipEventCreateWithFlags(&io_kernel_ev[b], hipEventDisableTiming));
+    if (!io_copy_ev[b]) HIPCHK(hipEventCreateWithFlags(&io_copy_ev[b], hipEventDisableTiming));
+  }
+  HIPCHK(hipStreamCreateWithFlags(&io_stream, hipStreamNonBlocking));
+}
+
+// The packed image of c rows (ops.h ReplayPackArgs) with the fields the caller asked for, in the order
+// state, next_state, action, reward, notdone, priority (`user`: the caller's six arrays, null = not wanted).
+struct PackImage {
+  size_t off[6], w[6], total = 0;
+  long long c;
+  bool want[6];
+  template <class P>
+  PackImage(const Replay& r, long long rows, P* const* user) : c(rows) {
+    const size_t width[6] = {(size_t)r.S, (size_t)r.S, (size_t)r.A, 1, 1, 1};
+    for (int f = 0; f < 6; ++f) {
+      w[f] = width[f];
+      want[f] = user[f] != nullptr;
+      off[f] = total;
+      if (want[f]) total += (size_t)c * w[f];
+    }
+  }
+  void point(ReplayPackArgs& a, float* img) const {
+    float** p[6] = {&a.p_state, &a.p_next_state, &a.p_action, &a.p_reward, &a.p_notdone, &a.p_priority};
+    for (int f = 0; f < 6; ++f) *p[f] = want[f] ? img + off[f] : nullptr;
+  }
+  void to_user(const float* img, float* const* user, long long row0) const {
+    for (int f = 0; f < 6; ++f)
+      if (want[f]) std::memcpy(user[f] + (size_t)row0 * w[f], img + off[f], (size_t)c * w[f] * sizeof(float));
+  }
+  void from_user(float* img, const float* const* user, long long row0) const {
+    for (int f = 0; f < 6; ++f)
+      if (want[f]) std::memcpy(img + off[f], user[f] + (size_t)row0 * w[f], (size_t)c * w[f] * sizeof(float));
+  }
+};
 
 }  // namespace rle
 
@@ -4584,6 +4647,7 @@ void Replay::wait_users() {
 
 using rle::Engine;
 using rle::Error;
+using rle::PackImage;
 using rle::Replay;
 
 struct rle_replay {
@@ -4669,6 +4733,14 @@ int rle_replay_destroy(rle_replay* r) {
     }
     (void)hipStreamSynchronize(r->r.stream);
     (void)hipStreamDestroy(r->r.stream);
+    if (r->r.io_stream) {
+      (void)hipStreamSynchronize(r->r.io_stream);
+      (void)hipStreamDestroy(r->r.io_stream);
+    }
+    for (int b = 0; b < 2; ++b) {
+      if (r->r.io_kernel_ev[b]) (void)hipEventDestroy(r->r.io_kernel_ev[b]);
+      if (r->r.io_copy_ev[b]) (void)hipEventDestroy(r->r.io_copy_ev[b]);
+    }
     delete r;
   });
 }
@@ -4922,28 +4994,162 @@ int rle_replay_reset_max_priority(rle_replay* h) {
 int rle_replay_gather(rle_replay* h, int n, const long long* ind, float* state, float* action, float* reward,
                       float* next_state, float* notdone) {
   return guard([&] {
+    REQUIRE(h && n >= 0 && (ind || n == 0), "gather: bad args");
     Replay& r = h->r;
-    r.drain_users();
-    HIPCHK(hipDeviceSynchronize());
-    std::vector<float> row(r.Sp);
-    for (int i = 0; i < n; ++i) {
-      const long long k = ind[i];
-      REQUIRE(k >= 0 && k < r.cap, "gather: index out of range");
-      if (state) {
-        HIPCHK(hipMemcpy(row.data(), r.state + k * r.Sp, r.Sp * 4, hipMemcpyDeviceToHost));
-        std::memcpy(state + (size_t)i * r.S, row.data(), r.S * 4);
-      }
-      if (next_state) {
-        HIPCHK(hipMemcpy(row.data(), r.next_state + k * r.Sp, r.Sp * 4, hipMemcpyDeviceToHost));
-        std::memcpy(next_state + (size_t)i * r.S, row.data(), r.S * 4);
-      }
-      if (action) {
-        HIPCHK(hipMemcpy(row.data(), r.action + k * r.Ap, r.Ap * 4, hipMemcpyDeviceToHost));
-        std::memcpy(action + (size_t)i * r.A, row.data(), r.A * 4);
-      }
-      if (reward) HIPCHK(hipMemcpy(reward + i, r.reward + k, 4, hipMemcpyDeviceToHost));
-      if (notdone) HIPCHK(hipMemcpy(notdone + i, r.notdone + k, 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) REQUIRE(ind[i] >= 0 && ind[i] < r.cap, "gather: index out of range");
+    if (n == 0) return;
+    HIPCHK(hipSetDevice(r.device));
+    r.wait_users();
+    // one index-mode pack per chunk of kIoRows rows into a device image, one copy of the image into pinned
+    // memory, then host copies into the caller's arrays (no per-row device copy)
+    float* user[6] = {state, next_state, action, reward, notdone, nullptr};
+    const long long cmax = std::min<long long>(n, Replay::kIoRows);
+    long long* dind = r.scratch.get<long long>("gather_ind", n);
+    float* dimg = r.scratch.get<float>("gather_img", (size_t)cmax * r.row_floats());
+    if (r.gather_host_floats < (size_t)cmax * r.row_floats()) {
+      r.gather_host_floats = (size_t)cmax * r.row_floats();
+      r.gather_host = static_cast<float*>(r.pin.alloc(r.gather_host_floats * sizeof(float)));
     }
+    HIPCHK(hipMemcpyAsync(dind, ind, (size_t)n * sizeof(long long), hipMemcpyHostToDevice, r.stream));
+    for (long long row0 = 0; row0 < n; row0 += cmax) {
+      const long long c = std::min<long long>(cmax, n - row0);
+      const PackImage L(r, c, user);
+      rle::ReplayPackArgs a = r.pack_args();
+      a.ind = dind + row0;
+      a.n = (int)c;
+      L.point(a, dimg);
+      HIPCHK(rle::launch_replay_pack(a, r.stream));
+      HIPCHK(hipMemcpyAsync(r.gather_host, dimg, L.total * sizeof(float), hipMemcpyDeviceToHost, r.stream));
+      HIPCHK(hipStreamSynchronize(r.stream));
+      L.to_user(r.gather_host, user, row0);
+    }
+  });
+}
+
+int rle_replay_io_rows(void) { return (int)Replay::kIoRows; }
+
+int rle_replay_export(rle_replay* h, long long first, long long count, float* state, float* action, float* reward,
+                      float* next_state, float* notdone, float* priority) {
+  return guard([&] {
+    REQUIRE(h, "export: null replay");
+    Replay& r = h->r;
+    REQUIRE(first >= 0 && count >= 0 && first + count <= r.cap, "export: slots first .. first+count-1 outside the ring");
+    REQUIRE(!priority || r.lap, "export: priority of a replay without LAP");
+    if (count == 0) return;
+    HIPCHK(hipSetDevice(r.device));
+    r.wait_users();
+    r.io_init();
+    float* user[6] = {state, next_state, action, reward, notdone, priority};
+    const long long R = Replay::kIoRows, nchunk = (count + R - 1) / R;
+    auto finish = [&](long long k) {  // chunk k: its copy done, then out of the pinned image
+      HIPCHK(hipEventSynchronize(r.io_copy_ev[k & 1]));
+      PackImage(r, std::min(R, count - k * R), user).to_user(r.io_host[k & 1], user, k * R);
+    };
+    for (long long k = 0; k < nchunk; ++k) {
+      const int b = (int)(k & 1);  // (image b is free: chunk k-2 left it in finish(k-2), an iteration ago)
+      const long long c = std::min(R, count - k * R);
+      const PackImage L(r, c, user);
+      rle::ReplayPackArgs a = r.pack_args();
+      a.first = first + k * R;
+      a.n = (int)c;
+      L.point(a, r.io_dev[b]);
+      HIPCHK(rle::launch_replay_pack(a, r.stream));
+      HIPCHK(hipEventRecord(r.io_kernel_ev[b], r.stream));
+      HIPCHK(hipStreamWaitEvent(r.io_stream, r.io_kernel_ev[b], 0));
+      HIPCHK(hipMemcpyAsync(r.io_host[b], r.io_dev[b], L.total * sizeof(float), hipMemcpyDeviceToHost, r.io_stream));
+      HIPCHK(hipEventRecord(r.io_copy_ev[b], r.io_stream));
+      if (k > 0) finish(k - 1);  // (under the kernel and copy of chunk k)
+    }
+    finish(nchunk - 1);
+  });
+}
+
+int rle_replay_import(rle_replay* h, long long first, long long count, const float* state, const float* action,
+                      const float* reward, const float* next_state, const float* notdone, const float* priority) {
+  return guard([&] {
+    REQUIRE(h, "import: null replay");
+    Replay& r = h->r;
+    REQUIRE(first >= 0 && count >= 0 && first + count <= r.cap, "import: slots first .. first+count-1 outside the ring");
+    REQUIRE(!priority || r.lap, "import: priority of a replay without LAP");
+    if (count == 0) return;
+    HIPCHK(hipSetDevice(r.device));
+    r.wait_users();
+    r.io_init();
+    const float* user[6] = {state, next_state, action, reward, notdone, priority};
+    const long long R = Replay::kIoRows, nchunk = (count + R - 1) / R;
+    ++r.version;
+    for (long long k = 0; k < nchunk; ++k) {
+      const int b = (int)(k & 1);
+      const long long c = std::min(R, count - k * R);
+      const PackImage L(r, c, user);
+      if (k >= 2) HIPCHK(hipEventSynchronize(r.io_copy_ev[b]));  // pinned image b: the copy of chunk k-2 has read it
+      L.from_user(r.io_host[b], user, k * R);
+      if (k >= 2) HIPCHK(hipStreamWaitEvent(r.io_stream, r.io_kernel_ev[b], 0));  // device image b: unpack k-2 done
+      HIPCHK(hipMemcpyAsync(r.io_dev[b], r.io_host[b], L.total * sizeof(float), hipMemcpyHostToDevice, r.io_stream));
+      HIPCHK(hipEventRecord(r.io_copy_ev[b], r.io_stream));
+      HIPCHK(hipStreamWaitEvent(r.stream, r.io_copy_ev[b], 0));
+      rle::ReplayPackArgs a = r.pack_args();
+      a.first = first + k * R;
+      a.n = (int)c;
+      L.point(a, r.io_dev[b]);
+      HIPCHK(rle::launch_replay_unpack(a, r.stream));
+      HIPCHK(hipEventRecord(r.io_kernel_ev[b], r.stream));
+    }
+    HIPCHK(hipStreamSynchronize(r.stream));
+  });
+}
+
+int rle_replay_set_state(rle_replay* h, long long ptr, long long size, float max_priority) {
+  return guard([&] {
+    REQUIRE(h, "set_state: null replay");
+    Replay& r = h->r;
+    REQUIRE(size >= 0 && size <= r.cap, "set_state: size outside 0..capacity");
+    REQUIRE(ptr >= 0 && ptr < r.cap, "set_state: ptr outside 0..capacity-1");
+    REQUIRE(std::isfinite(max_priority) && max_priority > 0.f, "set_state: max_priority must be finite and > 0");
+    HIPCHK(hipSetDevice(r.device));
+    r.wait_users();
+    r.ptr = ptr;
+    r.size = size;
+    HIPCHK(hipMemcpyAsync(r.size_d, &r.size, sizeof(long long), hipMemcpyHostToDevice, r.stream));
+    HIPCHK(hipMemcpyAsync(r.maxp_d, &max_priority, sizeof(float), hipMemcpyHostToDevice, r.stream));
+    HIPCHK(hipStreamSynchronize(r.stream));
+    if (r.lap) recompute_bsum(r);  // (rows at or past size count as 0)
+    ++r.version;
+  });
+}
+
+int rle_replay_copy(rle_replay* hd, rle_replay* hs) {
+  return guard([&] {
+    REQUIRE(hd && hs, "copy: null replay");
+    Replay &d = hd->r, &s = hs->r;
+    REQUIRE(d.cap == s.cap && d.S == s.S && d.A == s.A && d.lap == s.lap,
+            "copy: replays differ in capacity, state_dim, action_dim or lap");
+    if (hd == hs) return;
+    // the source quiescent (its users' steps and its own stream), then every array on the destination's stream
+    HIPCHK(hipSetDevice(s.device));
+    s.wait_users();
+    HIPCHK(hipStreamSynchronize(s.stream));
+    HIPCHK(hipSetDevice(d.device));
+    d.wait_users();
+    auto cp = [&](void* dst, const void* src, size_t bytes) {
+      if (d.device == s.device) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, d.stream));
+      else HIPCHK(hipMemcpyPeerAsync(dst, d.device, src, s.device, bytes, d.stream));
+    };
+    const size_t cap = (size_t)s.cap;
+    cp(d.state, s.state, cap * s.Sp * sizeof(float));
+    cp(d.next_state, s.next_state, cap * s.Sp * sizeof(float));
+    cp(d.action, s.action, cap * s.Ap * sizeof(float));
+    cp(d.reward, s.reward, cap * sizeof(float));
+    cp(d.notdone, s.notdone, cap * sizeof(float));
+    cp(d.priority, s.priority, cap * sizeof(float));
+    cp(d.bsum, s.bsum, (size_t)s.nblk * sizeof(double));
+    cp(d.ssum, s.ssum, (size_t)s.nblk * 64 * sizeof(double));
+    cp(d.maxp_d, s.maxp_d, sizeof(float));
+    cp(d.size_d, s.size_d, sizeof(long long));
+    HIPCHK(hipStreamSynchronize(d.stream));
+    d.ptr = s.ptr;
+    d.size = s.size;
+    ++d.version;
   });
 }
 

@@ -3486,6 +3486,112 @@ __global__ void rle_fill_kernel(float* state, float* next_state, float* action, 
   }
 }
 
+// Replay pack / unpack (ops.h ReplayPackArgs): ring rows <-> the unpadded staging image of export, import
+// and gather.  The grid is the tiles of state, next_state and action (pack_tile_rows rows each) followed by
+// 256-row tiles of the three per-row scalars.  A field tile crosses LDS: the ring side of it moves as one
+// 16-byte vector per lane (consecutive lanes, consecutive vectors of a 64-byte-aligned row), the packed side
+// as one dword per lane over the flattened [rows * W] (packed rows of 11, 17, 376, ... floats are not
+// 16-byte aligned).  Slots outside [0, cap) are never dereferenced (the host checks them first).
+struct PackTile {
+  int field;  // 0 state, 1 next_state, 2 action, 3 scalars
+  int tile;
+};
+__device__ __forceinline__ PackTile pack_tile_of(const ReplayPackArgs& a, int b) {
+  const int ts = (a.n + pack_tile_rows(a.Sp) - 1) / pack_tile_rows(a.Sp);
+  const int ta = (a.n + pack_tile_rows(a.Ap) - 1) / pack_tile_rows(a.Ap);
+  if (b < ts) return {0, b};
+  if (b < 2 * ts) return {1, b - ts};
+  if (b < 2 * ts + ta) return {2, b - 2 * ts};
+  return {3, b - 2 * ts - ta};
+}
+
+__device__ __forceinline__ void pack_field(const float* ring, float* packed, const ReplayPackArgs& a, int W, int Wp,
+                                           int tile, float4* lds) {
+  const int R = pack_tile_rows(Wp);
+  const int r0 = tile * R;
+  const int nr = min(R, a.n - r0);
+  const int w4 = Wp >> 2, u4 = (W + 3) >> 2;  // vectors per padded row; those that hold data
+  for (int i = threadIdx.x; i < nr * u4; i += blockDim.x) {
+    const int row = i / u4, c = i - row * u4;
+    const long long slot = a.ind ? a.ind[r0 + row] : a.first + r0 + row;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (slot >= 0 && slot < a.cap) v = reinterpret_cast<const float4*>(ring + slot * Wp)[c];
+    lds[row * w4 + c] = v;
+  }
+  __syncthreads();
+  const float* l = reinterpret_cast<const float*>(lds);
+  float* out = packed + (long long)r0 * W;
+  for (int e = threadIdx.x; e < nr * W; e += blockDim.x) {
+    const int row = e / W, col = e - row * W;
+    out[e] = l[row * Wp + col];
+  }
+}
+
+__device__ __forceinline__ void unpack_field(float* ring, const float* packed, const ReplayPackArgs& a, int W, int Wp,
+                                             int tile, float4* lds) {
+  const int R = pack_tile_rows(Wp);
+  const int r0 = tile * R;
+  const int nr = min(R, a.n - r0);
+  const int w4 = Wp >> 2, pad = Wp - W;
+  float* l = reinterpret_cast<float*>(lds);
+  const float* in = packed + (long long)r0 * W;
+  for (int e = threadIdx.x; e < nr * W; e += blockDim.x) {
+    const int row = e / W, col = e - row * W;
+    l[row * Wp + col] = in[e];
+  }
+  // the pad columns W .. Wp-1 stay zero in the ring (every writer keeps them so: the GEMMs read Wp columns)
+  for (int e = threadIdx.x; e < nr * pad; e += blockDim.x) {
+    const int row = e / pad, col = W + (e - row * pad);
+    l[row * Wp + col] = 0.f;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nr * w4; i += blockDim.x) {
+    const int row = i / w4, c = i - row * w4;
+    const long long slot = a.first + r0 + row;
+    if (slot >= 0 && slot < a.cap) reinterpret_cast<float4*>(ring + slot * Wp)[c] = lds[row * w4 + c];
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void rle_replay_pack(const ReplayPackArgs a) {
+  __shared__ float4 lds[kPackTile / 4];
+  const PackTile t = pack_tile_of(a, (int)blockIdx.x);
+  if (t.field == 0) {
+    if (a.p_state) pack_field(a.state, a.p_state, a, a.S, a.Sp, t.tile, lds);
+  } else if (t.field == 1) {
+    if (a.p_next_state) pack_field(a.next_state, a.p_next_state, a, a.S, a.Sp, t.tile, lds);
+  } else if (t.field == 2) {
+    if (a.p_action) pack_field(a.action, a.p_action, a, a.A, a.Ap, t.tile, lds);
+  } else {
+    const int i = t.tile * kThreads + (int)threadIdx.x;
+    if (i >= a.n) return;
+    const long long slot = a.ind ? a.ind[i] : a.first + i;
+    if (slot < 0 || slot >= a.cap) return;
+    if (a.p_reward) a.p_reward[i] = a.reward[slot];
+    if (a.p_notdone) a.p_notdone[i] = a.notdone[slot];
+    if (a.p_priority) a.p_priority[i] = a.priority[slot];
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void rle_replay_unpack(const ReplayPackArgs a) {
+  __shared__ float4 lds[kPackTile / 4];
+  const PackTile t = pack_tile_of(a, (int)blockIdx.x);
+  if (t.field == 0) {
+    if (a.p_state) unpack_field(a.state, a.p_state, a, a.S, a.Sp, t.tile, lds);
+  } else if (t.field == 1) {
+    if (a.p_next_state) unpack_field(a.next_state, a.p_next_state, a, a.S, a.Sp, t.tile, lds);
+  } else if (t.field == 2) {
+    if (a.p_action) unpack_field(a.action, a.p_action, a, a.A, a.Ap, t.tile, lds);
+  } else {
+    const int i = t.tile * kThreads + (int)threadIdx.x;
+    if (i >= a.n) return;
+    const long long slot = a.first + i;
+    if (slot < 0 || slot >= a.cap) return;
+    if (a.p_reward) a.reward[slot] = a.p_reward[i];
+    if (a.p_notdone) a.notdone[slot] = a.p_notdone[i];
+    if (a.p_priority) a.priority[slot] = a.p_priority[i];
+  }
+}
+
 // ---------------------------------------------------------------- host launchers
 
 // Workgroups of rle_level resident at once on the current device.
@@ -3588,6 +3694,26 @@ hipError_t launch_append(float* state, float* next_state, float* action, float* 
   hipLaunchKernelGGL(rle_append_kernel, dim3(count), dim3(256), 0, st, state, next_state, action, reward, notdone,
                      priority, st_s, st_ns, st_a, st_r, st_d, ptr, cap, count, Sp, Ap, max_priority, lap, bsum, ssum,
                      size_before);
+  return hipGetLastError();
+}
+static unsigned pack_grid(const ReplayPackArgs& a) {
+  const int ts = (a.n + pack_tile_rows(a.Sp) - 1) / pack_tile_rows(a.Sp);
+  const int ta = (a.n + pack_tile_rows(a.Ap) - 1) / pack_tile_rows(a.Ap);
+  return (unsigned)(2 * ts + ta + (a.n + kThreads - 1) / kThreads);
+}
+static bool pack_args_ok(const ReplayPackArgs& a) {
+  return a.n > 0 && a.cap > 0 && a.S > 0 && a.A > 0 && a.Sp % 16 == 0 && a.Ap % 16 == 0 && a.S <= a.Sp &&
+         a.A <= a.Ap && a.Sp <= kPackTile / 8 && a.Ap <= kPackTile / 8 &&
+         (a.ind || (a.first >= 0 && a.first + a.n <= a.cap));
+}
+hipError_t launch_replay_pack(const ReplayPackArgs& a, hipStream_t st) {
+  if (!pack_args_ok(a)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rle_replay_pack, dim3(pack_grid(a)), dim3(kThreads), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t launch_replay_unpack(const ReplayPackArgs& a, hipStream_t st) {
+  if (!pack_args_ok(a) || a.ind) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rle_replay_unpack, dim3(pack_grid(a)), dim3(kThreads), 0, st, a);
   return hipGetLastError();
 }
 hipError_t launch_act_chain(const ActChainArgs& a, hipStream_t st) {

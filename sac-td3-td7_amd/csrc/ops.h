@@ -640,4 +640,21 @@ struct Ctrl {
 
 enum Counter : int { CNT_ADAM_Q = 0, CNT_ADAM_PI = 1, CNT_ADAM_ENC = 2, CNT_RNG = 4, CNT_TAPE = 5 };
 
+// ---- replay pack / unpack (kernels.hip rle_replay_pack / rle_replay_unpack): n ring rows <-> one unpadded,
+// contiguous staging image [n][S] | [n][S] | [n][A] | [n] | [n] | [n] (export, import, gather).  The ring
+// side moves as 16-byte vectors (rows are 64-byte aligned: Sp, Ap are multiples of 16), the packed side as
+// coalesced dwords over the flattened [n * S]; a workgroup stages a tile of kPackTile floats in LDS between
+// the two.  Any packed pointer may be null (that field is skipped).
+constexpr int kPackTile = 8192;     // floats of LDS per workgroup (rows per tile: kPackTile / padded width)
+constexpr int kPackTileRows = 64;   // ... and at most this many rows
+struct ReplayPackArgs {
+  float *state, *next_state, *action, *reward, *notdone, *priority;  // the ring
+  float *p_state, *p_next_state, *p_action, *p_reward, *p_notdone, *p_priority;  // packed side
+  const long long* ind;  // pack only: n slot indices (device); null: slots first .. first + n - 1
+  long long first, cap;
+  int n, S, Sp, A, Ap;
+};
+// rows per workgroup tile of a field of padded width wp (host and device agree on the tile split)
+constexpr int pack_tile_rows(int wp) { return kPackTile / wp < kPackTileRows ? kPackTile / wp : kPackTileRows; }
+
 }  // namespace rle

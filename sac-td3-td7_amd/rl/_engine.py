@@ -15,6 +15,7 @@ import numpy as np
 RLE_TD7, RLE_TD3, RLE_SAC = 0, 1, 2
 RLE_EVAL_Q, RLE_EVAL_ZS, RLE_EVAL_ZSA = 0, 1, 2
 INFO_MAX = 8
+REPLAY_IO_ROWS = 8192  # rle_replay_io_rows(): rows per staging chunk of replay export / import
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RLE_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "librle.so")  # RLE_LIB: experiment builds
@@ -121,6 +122,11 @@ SIGNATURES = {
     "rle_replay_update_priority": (_int, [_vp, _int, _i64p, _f32p]),
     "rle_replay_reset_max_priority": (_int, [_vp]),
     "rle_replay_gather": (_int, [_vp, _int, _i64p, _f32p, _f32p, _f32p, _f32p, _f32p]),
+    "rle_replay_io_rows": (_int, []),
+    "rle_replay_export": (_int, [_vp, _ll, _ll, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]),
+    "rle_replay_import": (_int, [_vp, _ll, _ll, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]),
+    "rle_replay_set_state": (_int, [_vp, _ll, _ll, ctypes.c_float]),
+    "rle_replay_copy": (_int, [_vp, _vp]),
     "rle_create": (_int, [ctypes.POINTER(Config), ctypes.POINTER(_vp)]),
     "rle_destroy": (_int, [_vp]),
     "rle_plan_default": (_int, [ctypes.POINTER(Plan)]),
@@ -266,6 +272,37 @@ class Replay:
         d = np.empty(n, np.float32)
         _check(lib().rle_replay_gather(self.h, n, _ip(ind), _fp(s), _fp(a), _fp(r), _fp(s2), _fp(d)))
         return s, a, r, s2, d
+
+    def export_rows(self, first, count, priority=False):
+        """Slots first .. first+count-1 as unpadded fp32 arrays (rle_replay_export):
+        (state, action, reward, next_state, notdone), plus priority when asked (LAP replays)."""
+        first, n = int(first), int(count)
+        s = np.empty((n, self.S), np.float32)
+        a = np.empty((n, self.A), np.float32)
+        r = np.empty(n, np.float32)
+        s2 = np.empty((n, self.S), np.float32)
+        d = np.empty(n, np.float32)
+        p = np.empty(n, np.float32) if priority else None
+        _check(lib().rle_replay_export(self.h, first, n, _fp(s), _fp(a), _fp(r), _fp(s2), _fp(d), _fp(p)))
+        return (s, a, r, s2, d, p) if priority else (s, a, r, s2, d)
+
+    def import_rows(self, first, state, action, reward, next_state, notdone, priority=None):
+        """Host rows -> slots first .. (rle_replay_import); ptr, size and the LAP sums follow in set_state."""
+        n = len(reward)
+        s = _f32(state, (n, self.S))
+        a = _f32(action, (n, self.A))
+        r = _f32(reward, (n,))
+        s2 = _f32(next_state, (n, self.S))
+        d = _f32(notdone, (n,))
+        p = None if priority is None else _f32(priority, (n,))
+        _check(lib().rle_replay_import(self.h, int(first), n, _fp(s), _fp(a), _fp(r), _fp(s2), _fp(d), _fp(p)))
+
+    def set_state(self, ptr, size, max_priority):
+        _check(lib().rle_replay_set_state(self.h, int(ptr), int(size), float(max_priority)))
+
+    def copy_from(self, other: "Replay"):
+        """This ring := other (rle_replay_copy: device to device, also across two GPUs)."""
+        _check(lib().rle_replay_copy(self.h, other.h))
 
 
 class Engine:

@@ -19,22 +19,9 @@ import numpy as np
 from rl import _engine as E
 from rl.agent.abc import Agent
 from rl.nn.layout import AGENT_COPIES, AGENT_NETS, init_agent, layers
-from rl.replay_memory.base import BaseReplayMemory, DeviceBatch
+from rl.replay_memory.base import BaseReplayMemory, DeviceBatch, _device_index
 from rl.sampler import Sampler
 from rl.utils.envs import get_action_bias_scale, get_state_action_dims
-
-
-def _device_index(device) -> int:
-    if device is None:
-        return 0
-    if isinstance(device, int):
-        return device
-    s = str(device)
-    if s == "cpu":
-        return -1
-    if s.startswith("cuda") or s.startswith("hip"):
-        return int(s.split(":")[1]) if ":" in s else 0
-    raise ValueError(f"unsupported device {device!r}")
 
 
 class EngineAgent(Agent, Sampler):
@@ -126,7 +113,10 @@ class EngineAgent(Agent, Sampler):
             raise AssertionError("use_lap=True needs a LAPReplayMemory (td7.py:307-309)")
         if replay.device != self._device:
             raise ValueError(f"replay on device {replay.device}, agent on {self._device}")
-        if batch != self.batch_size or (self._replay is not None and self._replay is not replay):
+        # (graphs capture the bound ring: another replay, or the same one after replay.to() gave it a new
+        # ring, means a fresh engine)
+        moved = self._replay is replay and self.engine.replay is not replay.dev
+        if batch != self.batch_size or (self._replay is not None and self._replay is not replay) or moved:
             self._rebuild(batch)
         if self._replay is not replay:
             self.engine.bind(replay.dev)

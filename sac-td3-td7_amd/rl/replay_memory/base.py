@@ -14,7 +14,22 @@ from typing import Any
 import numpy as np
 
 from rl import _engine as E
+from rl.replay_memory import snapshot as S
 from rl.utils.envs import get_action_bias_scale, get_state_action_dims
+
+
+def _device_index(device) -> int:
+    """GPU index of a device spelling (None, k, "cuda", "cuda:k", "hip:k"); "cpu" is -1."""
+    if device is None:
+        return 0
+    if isinstance(device, int):
+        return device
+    s = str(device)
+    if s == "cpu":
+        return -1
+    if s.startswith("cuda") or s.startswith("hip"):
+        return int(s.split(":")[1]) if ":" in s else 0
+    raise ValueError(f"unsupported device {device!r}")
 
 
 class DeviceBatch(dict):
@@ -133,3 +148,120 @@ class BaseReplayMemory:
             data = {k: torch.from_numpy(v) for k, v in data.items()}
         self.ind = ind
         return DeviceBatch(data, ind, self)
+
+    # ---- save / restore / copy / move --------------------------------------
+    # The reference's replays are NumPy arrays (lap.py:18-29, simple.py:15-27): pickle, deepcopy and a
+    # checkpoint of them need no code.  Here the ring is in HBM behind a handle, so each is spelled out
+    # on the device pack kernels (rle_replay_export / _import / _copy).
+    def _meta(self) -> dict:
+        ptr, size, maxp = self.dev.state()
+        return S.make_meta(capacity=self.replay_buffer_size, state_dim=self.state_dim, action_dim=self.action_dim,
+                           lap=self.LAP, ptr=ptr, size=size, max_priority=maxp, env_id=self.env_id,
+                           action_bias=self.action_bias, action_scale=self.action_scale)
+
+    def _check_meta(self, meta) -> dict:
+        return S.validate_meta(meta, capacity=self.replay_buffer_size, state_dim=self.state_dim,
+                               action_dim=self.action_dim, lap=self.LAP)
+
+    def state_dict(self) -> dict:
+        """Everything sampling and appending depend on, as host data: ``meta`` (capacity, dims, lap, ptr,
+        size, max_priority, env_id, action map, format version), the arrays ``state``, ``action``,
+        ``reward``, ``next_state``, ``notdone`` (and ``priority`` for LAP) as rows ``[0, size)`` in slot
+        order, and the last indices ``ind``.  Staged appends are flushed first."""
+        self.flush()
+        meta = self._meta()
+        rows = self.dev.export_rows(0, meta["size"], priority=self.LAP)
+        sd = {"meta": meta}
+        sd.update(zip(S.field_names(self.LAP), rows))
+        ind = self.ind
+        sd["ind"] = None if ind is None else np.array(ind, np.int64)
+        return sd
+
+    def load_state_dict(self, sd: dict) -> "BaseReplayMemory":
+        """Restore a ``state_dict`` of a replay of the same capacity, dims and LAP-ness (ValueError
+        otherwise).  Engines bound to this replay redraw their prefetched batch."""
+        meta = self._check_meta(sd["meta"])
+        arrays = {k: np.ascontiguousarray(sd[k], np.float32) for k in S.field_names(self.LAP) if k in sd}
+        S.validate_arrays(meta, arrays)
+        self._stage = []
+        self.dev.import_rows(0, arrays["state"], arrays["action"], arrays["reward"], arrays["next_state"],
+                             arrays["notdone"], arrays.get("priority"))
+        self.dev.set_state(meta["ptr"], meta["size"], meta["max_priority"])
+        self.ind = sd.get("ind")
+        return self
+
+    def _host_attrs(self) -> dict:
+        return {k: v for k, v in self.__dict__.items() if k not in ("dev", "_stage", "_ind", "_ind_src")}
+
+    def _fresh(self, attrs: dict, device: int) -> None:
+        """An empty ring of this replay's settings on GPU ``device`` (no ``__init__``: the settings come
+        from a state or a snapshot, not from an environment table)."""
+        self.__dict__.update(attrs)
+        self.device = int(device)
+        self._stage, self._ind, self._ind_src = [], None, None
+        self.dev = E.Replay(self.replay_buffer_size, self.state_dim, self.action_dim, self.LAP, self.device)
+
+    def __getstate__(self) -> dict:
+        """Pickle goes through ``state_dict``: the whole replay is held in host memory (3.1 GB for 1M
+        Humanoid rows).  ``save`` / ``load`` stream it in chunks instead."""
+        return {"attrs": self._host_attrs(), "state": self.state_dict()}
+
+    def __setstate__(self, d: dict) -> None:
+        self._fresh(d["attrs"], d["attrs"].get("device", 0))
+        self.load_state_dict(d["state"])
+
+    def __deepcopy__(self, memo) -> "BaseReplayMemory":
+        """A new ring on the same GPU filled by one device-to-device copy (no host round trip)."""
+        import copy
+
+        self.flush()
+        new = type(self).__new__(type(self))
+        memo[id(self)] = new
+        new._fresh(copy.deepcopy(self._host_attrs(), memo), self.device)
+        new.dev.copy_from(self.dev)
+        new.ind = self.ind
+        return new
+
+    def to(self, device) -> "BaseReplayMemory":
+        """Move the ring to GPU k (``"cuda:k"``, ``"hip:k"`` or k, as ``EngineAgent.to``; "cpu" and the
+        current device are no-ops).  An agent that trains from this replay moves on its own:
+        ``agent.to(device)``."""
+        k = _device_index(device)
+        if k < 0 or k == self.device:
+            return self
+        self.flush()
+        ind = self.ind  # (read from the engine that drew it before its replay goes away)
+        new = E.Replay(self.replay_buffer_size, self.state_dim, self.action_dim, self.LAP, k)
+        new.copy_from(self.dev)
+        self.dev.close()
+        self.dev, self.device = new, k
+        self.ind = ind
+        return self
+
+    def save(self, path) -> None:
+        """Write the replay as a snapshot directory (rl/replay_memory/snapshot.py): ``meta.json`` and one
+        ``.npy`` per array, streamed ``REPLAY_IO_ROWS`` rows at a time, so host memory stays bounded by
+        one chunk whatever the replay's size."""
+        self.flush()
+        meta = self._meta()
+        names = S.field_names(self.LAP)
+        with S.SnapshotWriter(path, meta, self.ind) as w:
+            for first in range(0, meta["size"], E.REPLAY_IO_ROWS):
+                c = min(E.REPLAY_IO_ROWS, meta["size"] - first)
+                w.write(dict(zip(names, self.dev.export_rows(first, c, priority=self.LAP))))
+
+    @classmethod
+    def load(cls, path, device=0) -> "BaseReplayMemory":
+        """Read a snapshot directory written by ``save`` into a new replay on GPU ``device``."""
+        meta, ind, chunks = S.read_snapshot(path, E.REPLAY_IO_ROWS, lap=cls.LAP)
+        new = cls.__new__(cls)
+        new._fresh({"replay_buffer_size": meta["capacity"], "env_id": meta["env_id"],
+                    "state_dim": meta["state_dim"], "action_dim": meta["action_dim"],
+                    "action_bias": np.asarray(meta["action_bias"], np.float32),
+                    "action_scale": np.asarray(meta["action_scale"], np.float32)}, max(_device_index(device), 0))
+        for first, c in chunks:
+            new.dev.import_rows(first, c["state"], c["action"], c["reward"], c["next_state"], c["notdone"],
+                                c.get("priority"))
+        new.dev.set_state(meta["ptr"], meta["size"], meta["max_priority"])
+        new.ind = ind
+        return new
