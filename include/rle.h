@@ -203,6 +203,40 @@ int rle_set_param(rle_engine* e, const char* net, const char* name, const float*
 int rle_get_adam(rle_engine* e, const char* net, const char* name, int which, float* out, long long n);
 int rle_set_adam(rle_engine* e, const char* net, const char* name, int which, const float* in,
                  long long n);
+/* The same state in ONE device pass.  The per-tensor entries above make a host round trip per tensor (a TD7
+ * agent has 84 parameter and 72 moment tensors); these move every selected tensor with one launch of a pack
+ * kernel and one copy through a pinned image.  `what`: a mask of RLE_STATE_*.  The packed state is the
+ * concatenation of the logical row-major tensors (the arrays rle_get_param / rle_get_adam return), in the
+ * order of rle_state_toc: arenas in mask-bit order (params, m, v); within one, nets in the engine's order,
+ * layers in order, weight before bias, and for SAC "tmp" / "log_alpha" last.  The Adam arenas list only the
+ * nets that have an optimiser (policy, q1, q2, TD7's encoder; SAC's tmp). */
+#define RLE_STATE_PARAMS 1
+#define RLE_STATE_ADAM_M 2
+#define RLE_STATE_ADAM_V 4
+#define RLE_STATE_ALL 7
+typedef struct rle_state_entry {
+  char net[32];         /* "policy", "target_q1", ..., "tmp" */
+  char name[32];        /* "q01.weight", "mlp.2.bias", "log_alpha" */
+  int arena;            /* 0 params, 1 Adam m, 2 Adam v */
+  int reserved;
+  long long offset;     /* floats from the start of the packed state */
+  long long numel;
+} rle_state_entry;
+/* Table of contents of the packed state of `what`: up to cap records into entries (may be NULL with cap 0),
+ * *n = the number of tensors.  Entry i + 1 starts where entry i ends; the last one ends at the state's size
+ * in floats.  No GPU call. */
+int rle_state_toc(rle_engine* e, int what, rle_state_entry* entries, int cap, int* n);
+/* Packed state -> out [n_floats] / in [n_floats] -> the engine.  n_floats must be the size rle_state_toc
+ * reports (RLE_EINVAL otherwise, as for an empty or unknown mask).  Export: waits for enqueued steps, one pack
+ * launch, one copy, one sync.  Import: the reverse; parameters are written as both GEMM images, every padded
+ * row and column as zero, and the engine's derived state is invalidated as rle_set_param does. */
+int rle_state_export(rle_engine* e, int what, float* out, long long n_floats);
+int rle_state_import(rle_engine* e, int what, const float* in, long long n_floats);
+/* Agent.load_state_dict(agent) (td7.py:114-125, td3.py:94-100, sac.py:101-107) on the device(s): every
+ * network's parameters of src into dst -- not the Adam moments, counters, value bounds, RNG position or SAC
+ * log_alpha.  Same algorithm and identical layer shapes required (RLE_EINVAL); batch size and plan may differ,
+ * and the two may live on different GPUs (a peer copy).  No host round trip. */
+int rle_copy_nets(rle_engine* dst, rle_engine* src);
 /* Device counters: [0] critic Adam t, [1] policy Adam t, [2] encoder Adam t, [3] n_runs,
  * [4] rng step, [5] SAC temperature Adam t. */
 int rle_get_counters(rle_engine* e, long long* out6);
@@ -311,7 +345,8 @@ int rle_aql_wait_plan(double expected_us, double elapsed_us, double timeout_s, d
  * and no doorbell publishes a run of packets that straddles the ring's end.  0 when every check holds. */
 int rle_aql_selftest(void);
 /* Copy all weights/optimizer state/counters of src into dst (checkpoint agent,
- * ckpt_agent.load_state_dict(agent), run_w_checkpoint.py:140). Same config required. */
+ * ckpt_agent.load_state_dict(agent), run_w_checkpoint.py:140), and the act path's exploration counter
+ * (rle_get_act_counter).  Same algorithm and identical layer shapes required; the batch size may differ. */
 int rle_copy_state(rle_engine* dst, rle_engine* src);
 int rle_synchronize(rle_engine* e);
 

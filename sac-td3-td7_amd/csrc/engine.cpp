@@ -52,6 +52,8 @@ hipError_t launch_fill(float* state, float* next_state, float* action, float* re
                        hipStream_t st);
 hipError_t launch_replay_pack(const ReplayPackArgs& a, hipStream_t st);
 hipError_t launch_replay_unpack(const ReplayPackArgs& a, hipStream_t st);
+hipError_t launch_state_pack(const StatePackArgs& a, hipStream_t st);
+hipError_t launch_state_unpack(const StatePackArgs& a, hipStream_t st);
 
 static thread_local std::string g_err;
 
@@ -2094,6 +2096,122 @@ struct Engine {
       HIPCHK(hipMemcpy(dt, tim.data(), img * 4, hipMemcpyHostToDevice));
       if (which == 0) HIPCHK(hipMemcpy(dn, nim.data(), img * 4, hipMemcpyHostToDevice));
     }
+  }
+
+  // ---------------------------------------------------------------- packed state (rle_state_*)
+  // Table of contents of the packed state of a mask of RLE_STATE_* (rle.h), and the tables the pack kernels
+  // run from (ops.h StateDesc / StateTile), built once per mask from nets / Layer.  Host only until
+  // state_io_init uploads them.
+  struct StateToc {
+    std::vector<rle_state_entry> entries;
+    std::vector<StateDesc> desc;
+    std::vector<StateTile> tiles;
+    long long total = 0;  // floats of the packed state
+    StateDesc* d_desc = nullptr;
+    StateTile* d_tiles = nullptr;
+  };
+  std::map<int, StateToc> state_tocs;
+  float* state_dev = nullptr;   // packed image of the full mask (device / pinned)
+  float* state_host = nullptr;
+  static bool has_optimizer(const std::string& n) { return n == "policy" || n == "q1" || n == "q2" || n == "encoder"; }
+
+  StateToc& state_toc(int what) {
+    REQUIRE(what > 0 && what <= RLE_STATE_ALL, "state: `what` must be a non-empty mask of RLE_STATE_PARAMS / _ADAM_M / _ADAM_V");
+    auto it = state_tocs.find(what);
+    if (it != state_tocs.end()) return it->second;
+    StateToc t;
+    auto add = [&](const std::string& netn, const std::string& name, int arena, StateDesc d, long long numel) {
+      rle_state_entry en{};
+      std::snprintf(en.net, sizeof en.net, "%s", netn.c_str());
+      std::snprintf(en.name, sizeof en.name, "%s", name.c_str());
+      en.arena = arena;
+      en.offset = t.total;
+      en.numel = numel;
+      d.p_off = t.total;
+      const size_t img = d.kind ? (size_t)d.n_img : (size_t)d.rb * d.cb * 256;
+      REQUIRE((size_t)d.wt_off + img <= 3 * nP && (d.wn_off < 0 || (size_t)d.wn_off + img <= 3 * nP),
+              "state: a tensor image outside the parameter arenas");
+      const int nt = d.kind ? 1 : d.rb * cdiv(d.cb * 16, kStateCols);
+      for (int s = 0; s < nt; ++s) t.tiles.push_back({(int)t.desc.size(), s});
+      t.desc.push_back(d);
+      t.entries.push_back(en);
+      t.total += numel;
+    };
+    for (int arena = 0; arena < 3; ++arena) {
+      if (!((what >> arena) & 1)) continue;
+      const long long base = (long long)arena * (long long)nP;
+      for (const Net& n : nets) {
+        if (arena && !has_optimizer(n.name)) continue;
+        for (const Layer& L : n.layers) {
+          REQUIRE(L.seg_w.size() <= (size_t)kStateSegs, "state: a layer with more input segments than the pack kernels take");
+          StateDesc w{};
+          w.kind = 0;
+          w.wt_off = base + (long long)L.wt_off;
+          w.wn_off = arena == 0 ? (long long)L.wn_off : -1;  // (Adam m / v live at the T offsets only)
+          w.rb = L.rb;
+          w.cb = L.cb;
+          w.out = L.out;
+          w.nseg = (int)L.seg_w.size();
+          for (int s = 0; s < w.nseg; ++s) {
+            w.seg_w[s] = L.seg_w[s];
+            w.seg_p[s] = L.seg_p[s];
+            w.klog += L.seg_w[s];
+          }
+          add(n.name, L.wname, arena, w, (long long)L.out * w.klog);
+          StateDesc b{};
+          b.kind = 1;
+          b.wt_off = base + (long long)L.b_off;
+          b.wn_off = -1;
+          b.out = L.out;
+          b.n_img = 16 * L.rb;
+          add(n.name, L.bname, arena, b, L.out);
+        }
+      }
+      if (algo == RLE_SAC) {  // the log_alpha slot: one float
+        StateDesc a{};
+        a.kind = 1;
+        a.wt_off = base + (long long)(nP - 4);
+        a.wn_off = -1;
+        a.out = a.n_img = 1;
+        add("tmp", "log_alpha", arena, a, 1);
+      }
+    }
+    return state_tocs.emplace(what, std::move(t)).first->second;
+  }
+
+  // the mask's tables on the device, and the staging images (sized once, for the full mask)
+  void state_io_init(StateToc& t) {
+    if (!state_dev) {
+      const size_t n = (size_t)state_toc(RLE_STATE_ALL).total;
+      state_dev = mem.make<float>(n);
+      state_host = static_cast<float*>(pin.alloc(n * sizeof(float)));
+    }
+    if (t.d_desc) return;
+    t.d_desc = mem.make<StateDesc>(t.desc.size());
+    t.d_tiles = mem.make<StateTile>(t.tiles.size());
+    HIPCHK(hipMemcpy(t.d_desc, t.desc.data(), t.desc.size() * sizeof(StateDesc), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(t.d_tiles, t.tiles.data(), t.tiles.size() * sizeof(StateTile), hipMemcpyHostToDevice));
+  }
+  StatePackArgs state_args(const StateToc& t) const {
+    StatePackArgs a{};
+    a.P = P;
+    a.packed = state_dev;
+    a.desc = t.d_desc;
+    a.tiles = t.d_tiles;
+    a.ntiles = (int)t.tiles.size();
+    return a;
+  }
+  // the same networks, layer by layer (the parameter layout depends on nothing else)
+  bool same_shapes(const Engine& o) const {
+    if (algo != o.algo || nP != o.nP || nets.size() != o.nets.size()) return false;
+    for (size_t i = 0; i < nets.size(); ++i) {
+      if (nets[i].name != o.nets[i].name || nets[i].layers.size() != o.nets[i].layers.size()) return false;
+      for (size_t l = 0; l < nets[i].layers.size(); ++l) {
+        const Layer &a = nets[i].layers[l], &b = o.nets[i].layers[l];
+        if (a.wname != b.wname || a.out != b.out || a.seg_w != b.seg_w || a.wt_off != b.wt_off) return false;
+      }
+    }
+    return true;
   }
 
   // ---------------------------------------------------------------- buffers
@@ -5831,11 +5949,77 @@ int rle_aql_wait_plan(double expected_us, double elapsed_us, double timeout_s, d
   return act;
 }
 
+int rle_state_toc(rle_engine* h, int what, rle_state_entry* entries, int cap, int* n) {
+  return guard([&] {
+    REQUIRE(h && n && cap >= 0 && (entries || cap == 0), "state_toc: bad args");
+    const Engine::StateToc& t = h->e->state_toc(what);
+    *n = (int)t.entries.size();
+    for (int i = 0; i < cap && i < *n; ++i) entries[i] = t.entries[i];
+  });
+}
+
+int rle_state_export(rle_engine* h, int what, float* out, long long n_floats) {
+  return guard([&] {
+    REQUIRE(h && out, "state_export: null");
+    Engine& e = drained(h);
+    Engine::StateToc& t = e.state_toc(what);
+    REQUIRE(n_floats == t.total, "state_export: n_floats " + std::to_string(n_floats) + ", the packed state has " +
+                                     std::to_string(t.total) + " floats");
+    HIPCHK(hipSetDevice(e.cfg.device));
+    e.state_io_init(t);
+    const size_t bytes = (size_t)t.total * sizeof(float);
+    HIPCHK(rle::launch_state_pack(e.state_args(t), e.stream));
+    HIPCHK(hipMemcpyAsync(e.state_host, e.state_dev, bytes, hipMemcpyDeviceToHost, e.stream));
+    HIPCHK(hipStreamSynchronize(e.stream));
+    std::memcpy(out, e.state_host, bytes);
+  });
+}
+
+int rle_state_import(rle_engine* h, int what, const float* in, long long n_floats) {
+  return guard([&] {
+    REQUIRE(h && in, "state_import: null");
+    Engine& e = drained(h);
+    Engine::StateToc& t = e.state_toc(what);
+    REQUIRE(n_floats == t.total, "state_import: n_floats " + std::to_string(n_floats) + ", the packed state has " +
+                                     std::to_string(t.total) + " floats");
+    HIPCHK(hipSetDevice(e.cfg.device));
+    e.state_io_init(t);
+    const size_t bytes = (size_t)t.total * sizeof(float);
+    HIPCHK(hipStreamSynchronize(e.stream));  // (the pinned image: no earlier copy still reads it)
+    std::memcpy(e.state_host, in, bytes);
+    HIPCHK(hipMemcpyAsync(e.state_dev, e.state_host, bytes, hipMemcpyHostToDevice, e.stream));
+    HIPCHK(rle::launch_state_unpack(e.state_args(t), e.stream));
+    HIPCHK(hipStreamSynchronize(e.stream));
+    e.fold_dirty = true;  // (as rle_set_param: the folded target-critic weights follow the parameters)
+  });
+}
+
+int rle_copy_nets(rle_engine* dst, rle_engine* src) {
+  return guard([&] {
+    REQUIRE(dst && src, "copy_nets: null engine");
+    Engine& d = drained(dst);
+    Engine& s = drained(src);
+    REQUIRE(d.same_shapes(s), "copy_nets: the engines differ in algorithm or layer shapes");
+    if (dst == src) return;
+    HIPCHK(hipSetDevice(s.cfg.device));
+    HIPCHK(hipStreamSynchronize(s.stream));
+    HIPCHK(hipSetDevice(d.cfg.device));
+    // every net's N image | T image | bias is one run of the parameter arena; the log_alpha slot behind it stays
+    const size_t bytes = (size_t)(d.nP - 4) * sizeof(float);
+    if (d.cfg.device == s.cfg.device) HIPCHK(hipMemcpyAsync(d.P, s.P, bytes, hipMemcpyDeviceToDevice, d.stream));
+    else HIPCHK(hipMemcpyPeerAsync(d.P, d.cfg.device, s.P, s.cfg.device, bytes, d.stream));
+    HIPCHK(hipStreamSynchronize(d.stream));
+    d.fold_dirty = true;
+  });
+}
+
 int rle_copy_state(rle_engine* dst, rle_engine* src) {
   return guard([&] {
     Engine& d = drained(dst);
     Engine& s = drained(src);
-    REQUIRE(d.nP == s.nP && d.algo == s.algo, "copy_state: config mismatch");
+    // (nP and the algorithm alone would also pass two MLPs whose widths are a permutation of each other)
+    REQUIRE(d.same_shapes(s), "copy_state: config mismatch");
+    d.act_counter = s.act_counter;
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(d.P, s.P, 3 * d.nP * sizeof(float), hipMemcpyDeviceToDevice));
     rle::Ctrl c;
@@ -5844,6 +6028,7 @@ int rle_copy_state(rle_engine* dst, rle_engine* src) {
     d.n_runs = s.n_runs;
     d.primed = false;
     d.fold_dirty = true;
+    d.refresh_adam_scalars();  // (as rle_set_counters: both batch sets' copies, for readers outside a step)
   });
 }
 

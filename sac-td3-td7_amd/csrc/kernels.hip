@@ -3592,6 +3592,108 @@ __global__ __launch_bounds__(kThreads) void rle_replay_unpack(const ReplayPackAr
   }
 }
 
+// Agent state pack / unpack (ops.h StatePackArgs): the tensors of the params | m | v arenas <-> the packed
+// image of logical row-major tensors.  Workgroup b serves tiles[b].  A weight sub-tile (one 16-row block x up
+// to kStateCols padded columns) crosses LDS as [16][kStateStride]: the image side of it moves as one 16-byte
+// vector per lane (64 consecutive lanes, one 1 KB block), the packed side as one dword per lane along the
+// logical rows (rows of 393 or 17 floats are not 16-byte aligned).  The host builds the tables from the
+// engine's own layout, so every offset lies inside the arenas and the packed image.
+
+// logical column of padded column pc of a weight; -1 in a segment's pad
+__device__ __forceinline__ int state_logical_col(const StateDesc& d, int pc) {
+  int p0 = 0, l0 = 0;
+  for (int s = 0; s < d.nseg; ++s) {
+    if (pc < p0 + d.seg_p[s]) return pc - p0 < d.seg_w[s] ? l0 + pc - p0 : -1;
+    p0 += d.seg_p[s];
+    l0 += d.seg_w[s];
+  }
+  return -1;
+}
+
+struct StateSub {
+  int rblk, cb0, nb, nr;  // row block; first column block, column blocks; logical rows in the block
+};
+__device__ __forceinline__ StateSub state_sub_of(const StateDesc& d, int sub) {
+  const int per = kStateCols / 16;
+  const int nchunk = (d.cb + per - 1) / per;
+  StateSub s;
+  s.rblk = sub / nchunk;
+  s.cb0 = (sub - s.rblk * nchunk) * per;
+  s.nb = min(per, d.cb - s.cb0);
+  s.nr = min(16, d.out - s.rblk * 16);
+  return s;
+}
+
+__global__ __launch_bounds__(kThreads) void rle_state_pack(const StatePackArgs a) {
+  __shared__ float4 lds[16 * kStateStride / 4];
+  if ((int)blockIdx.x >= a.ntiles) return;
+  const StateTile t = a.tiles[blockIdx.x];
+  const StateDesc& d = a.desc[t.desc];
+  float* packed = a.packed + d.p_off;
+  if (d.kind == 1) {
+    const float* img = a.P + d.wt_off;
+    for (int i = threadIdx.x; i < d.out; i += blockDim.x) packed[i] = img[i];
+    return;
+  }
+  const StateSub s = state_sub_of(d, t.sub);
+  float* l = reinterpret_cast<float*>(lds);
+  const float* timg = a.P + d.wt_off;
+  for (int i = threadIdx.x; i < s.nb * 64; i += blockDim.x) {
+    const int blk = i >> 6, v = i & 63, q = v >> 4, cc = v & 15;  // T block: vector v = rows 4q .. 4q+3 of column cc
+    const float4 x = reinterpret_cast<const float4*>(timg + ((long long)(s.cb0 + blk) * d.rb + s.rblk) * 256)[v];
+    float* dst = l + 4 * q * kStateStride + blk * 16 + cc;
+    dst[0] = x.x;
+    dst[kStateStride] = x.y;
+    dst[2 * kStateStride] = x.z;
+    dst[3 * kStateStride] = x.w;
+  }
+  __syncthreads();
+  const int Wc = s.nb * 16;
+  for (int e = threadIdx.x; e < s.nr * Wc; e += blockDim.x) {
+    const int row = e / Wc, c = e - row * Wc;
+    const int lc = state_logical_col(d, s.cb0 * 16 + c);
+    if (lc >= 0) packed[(long long)(s.rblk * 16 + row) * d.klog + lc] = l[row * kStateStride + c];
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void rle_state_unpack(const StatePackArgs a) {
+  __shared__ float4 lds[16 * kStateStride / 4];
+  if ((int)blockIdx.x >= a.ntiles) return;
+  const StateTile t = a.tiles[blockIdx.x];
+  const StateDesc& d = a.desc[t.desc];
+  const float* packed = a.packed + d.p_off;
+  if (d.kind == 1) {  // (the image's tail past `out` stays zero, as the padded rows of the weights do)
+    float* img = a.P + d.wt_off;
+    for (int i = threadIdx.x; i < d.n_img; i += blockDim.x) img[i] = i < d.out ? packed[i] : 0.f;
+    return;
+  }
+  const StateSub s = state_sub_of(d, t.sub);
+  float* l = reinterpret_cast<float*>(lds);
+  const int Wc = s.nb * 16;
+  // whole blocks are rewritten: padded rows, padded columns and segment pads get zeros (the GEMM
+  // reductions run over them)
+  for (int e = threadIdx.x; e < 16 * Wc; e += blockDim.x) {
+    const int row = e / Wc, c = e - row * Wc;
+    const int lc = row < s.nr ? state_logical_col(d, s.cb0 * 16 + c) : -1;
+    l[row * kStateStride + c] = lc >= 0 ? packed[(long long)(s.rblk * 16 + row) * d.klog + lc] : 0.f;
+  }
+  __syncthreads();
+  float* timg = a.P + d.wt_off;
+  for (int i = threadIdx.x; i < s.nb * 64; i += blockDim.x) {
+    const int blk = i >> 6, v = i & 63, q = v >> 4, cc = v & 15;
+    const float* src = l + 4 * q * kStateStride + blk * 16 + cc;
+    const float4 x = make_float4(src[0], src[kStateStride], src[2 * kStateStride], src[3 * kStateStride]);
+    reinterpret_cast<float4*>(timg + ((long long)(s.cb0 + blk) * d.rb + s.rblk) * 256)[v] = x;
+  }
+  if (d.wn_off < 0) return;
+  float* nimg = a.P + d.wn_off;
+  for (int i = threadIdx.x; i < s.nb * 64; i += blockDim.x) {
+    const int blk = i >> 6, v = i & 63, cq = v >> 4, r = v & 15;  // N block: vector v = columns 4cq .. 4cq+3 of row r
+    const float4 x = lds[(r * kStateStride + blk * 16 + 4 * cq) >> 2];
+    reinterpret_cast<float4*>(nimg + ((long long)s.rblk * d.cb + s.cb0 + blk) * 256)[v] = x;
+  }
+}
+
 // ---------------------------------------------------------------- host launchers
 
 // Workgroups of rle_level resident at once on the current device.
@@ -3714,6 +3816,19 @@ hipError_t launch_replay_pack(const ReplayPackArgs& a, hipStream_t st) {
 hipError_t launch_replay_unpack(const ReplayPackArgs& a, hipStream_t st) {
   if (!pack_args_ok(a) || a.ind) return hipErrorInvalidValue;
   hipLaunchKernelGGL(rle_replay_unpack, dim3(pack_grid(a)), dim3(kThreads), 0, st, a);
+  return hipGetLastError();
+}
+static bool state_args_ok(const StatePackArgs& a) {
+  return a.P && a.packed && a.desc && a.tiles && a.ntiles > 0;
+}
+hipError_t launch_state_pack(const StatePackArgs& a, hipStream_t st) {
+  if (!state_args_ok(a)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rle_state_pack, dim3((unsigned)a.ntiles), dim3(kThreads), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t launch_state_unpack(const StatePackArgs& a, hipStream_t st) {
+  if (!state_args_ok(a)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rle_state_unpack, dim3((unsigned)a.ntiles), dim3(kThreads), 0, st, a);
   return hipGetLastError();
 }
 hipError_t launch_act_chain(const ActChainArgs& a, hipStream_t st) {

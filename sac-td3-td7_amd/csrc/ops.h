@@ -657,4 +657,37 @@ struct ReplayPackArgs {
 // rows per workgroup tile of a field of padded width wp (host and device agree on the tile split)
 constexpr int pack_tile_rows(int wp) { return kPackTile / wp < kPackTileRows ? kPackTile / wp : kPackTileRows; }
 
+// ---- agent state pack / unpack (kernels.hip rle_state_pack / rle_state_unpack): the selected tensors of the
+// params | m | v arenas <-> one packed image of logical row-major tensors (state_dict() layout: weights
+// [out][sum seg_w] without the per-segment padding, biases [out], SAC log_alpha one float).  One launch covers
+// every tensor: workgroup b serves tile `tiles[b]` = {descriptor, sub-tile}.  A weight sub-tile is one 16-row
+// block x up to kStateCols padded columns: the image side moves as one 16-byte vector of a 1 KB block per lane,
+// the packed side as dwords along the logical rows, with an LDS tile in between.  A vector tensor (bias,
+// log_alpha) is one tile.  Unpack rewrites whole blocks, so every padded row, column and segment pad gets 0.
+constexpr int kStateCols = 512;              // padded columns per weight sub-tile (32 blocks)
+constexpr int kStateStride = kStateCols + 4; // LDS row stride (floats; a multiple of 4)
+constexpr int kStateSegs = 4;
+struct StateDesc {
+  long long wt_off;   // weight: T image; vector: the image -- floats from P (arena base included)
+  long long wn_off;   // weight: N image, written by unpack (params arena); < 0: none (Adam m / v)
+  long long p_off;    // floats from the packed image's start
+  int kind;           // 0 weight, 1 vector
+  int rb, cb;         // weight: 16-row / 16-column blocks
+  int out;            // logical rows (vector: logical length)
+  int klog;           // weight: logical row length, sum seg_w
+  int n_img;          // vector: image length (16 rb; log_alpha 1), the tail past `out` is zero
+  int nseg;
+  int seg_w[kStateSegs], seg_p[kStateSegs];
+};
+struct StateTile {
+  int desc, sub;      // weight sub-tile: row block * chunks + chunk (chunk: kStateCols padded columns)
+};
+struct StatePackArgs {
+  float* P;                // the engine's params | m | v arenas
+  float* packed;
+  const StateDesc* desc;
+  const StateTile* tiles;
+  int ntiles;
+};
+
 }  // namespace rle

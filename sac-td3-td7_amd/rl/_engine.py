@@ -7,8 +7,10 @@ fails to load, every engine-backed object raises.
 
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
+import threading
 
 import numpy as np
 
@@ -108,6 +110,31 @@ def plan_dict(p: Plan) -> dict:
     return d
 
 
+STATE_PARAMS, STATE_ADAM_M, STATE_ADAM_V, STATE_ALL = 1, 2, 4, 7  # RLE_STATE_* masks of rle_state_*
+
+_scratch = np.empty(0, np.float32)
+_scratch_lock = threading.Lock()
+
+
+@contextlib.contextmanager
+def state_scratch(n):
+    """A process-wide fp32 host array of n elements for assembling a packed state that is imported at
+    once (unpickling makes a new engine per agent: an array per engine would be allocated and freed, tens
+    of MB, on every load).  Grown on demand, never shrunk; held under a lock while in use."""
+    global _scratch
+    with _scratch_lock:
+        if _scratch.size < n:
+            _scratch = np.empty(n, np.float32)
+        yield _scratch[:n]
+
+
+class StateEntry(ctypes.Structure):
+    """Mirror of ``rle_state_entry`` (include/rle.h): one tensor of a packed agent state."""
+
+    _fields_ = [("net", ctypes.c_char * 32), ("name", ctypes.c_char * 32), ("arena", _int), ("reserved", _int),
+                ("offset", _ll), ("numel", _ll)]
+
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "rle_last_error": (_cs, []),
@@ -138,6 +165,10 @@ SIGNATURES = {
     "rle_set_param": (_int, [_vp, _cs, _cs, _f32p, _ll]),
     "rle_get_adam": (_int, [_vp, _cs, _cs, _int, _f32p, _ll]),
     "rle_set_adam": (_int, [_vp, _cs, _cs, _int, _f32p, _ll]),
+    "rle_state_toc": (_int, [_vp, _int, ctypes.POINTER(StateEntry), _int, ctypes.POINTER(_int)]),
+    "rle_state_export": (_int, [_vp, _int, _f32p, _ll]),
+    "rle_state_import": (_int, [_vp, _int, _f32p, _ll]),
+    "rle_copy_nets": (_int, [_vp, _vp]),
     "rle_get_counters": (_int, [_vp, _i64p]),
     "rle_set_counters": (_int, [_vp, _i64p]),
     "rle_get_act_counter": (_int, [_vp, ctypes.POINTER(ctypes.c_uint64)]),
@@ -366,6 +397,49 @@ class Engine:
     def set_adam(self, net, name, which, value):
         v = _f32(value).ravel()
         _check(lib().rle_set_adam(self.h, net.encode(), name.encode(), which, _fp(v), v.size))
+
+    def state_toc(self, what=STATE_ALL):
+        """Table of contents of the packed state of mask ``what`` (rle_state_toc): a list of
+        (net, name, arena, offset, numel), arena 0 params / 1 Adam m / 2 Adam v, offsets in floats."""
+        tocs = self.__dict__.setdefault("_state_tocs", {})
+        if what not in tocs:
+            n = _int()
+            _check(lib().rle_state_toc(self.h, what, None, 0, ctypes.byref(n)))
+            ent = (StateEntry * n.value)()
+            _check(lib().rle_state_toc(self.h, what, ent, n.value, ctypes.byref(n)))
+            tocs[what] = [(e.net.decode(), e.name.decode(), e.arena, e.offset, e.numel) for e in ent]
+        return tocs[what]
+
+    def state_size(self, what=STATE_ALL):
+        toc = self.state_toc(what)
+        return toc[-1][3] + toc[-1][4]
+
+    def state_buffer(self, what=STATE_ALL):
+        """This engine's reusable host array for a packed state of ``what`` (allocated once, for the full
+        mask): for callers that consume a state at once, as pickling does -- the next user overwrites it."""
+        buf = self.__dict__.get("_state_buf")
+        if buf is None:
+            buf = self._state_buf = np.empty(self.state_size(STATE_ALL), np.float32)
+        return buf[:self.state_size(what)]
+
+    def state_export(self, what=STATE_ALL, out=None):
+        """The packed state of ``what`` as one fp32 array (rle_state_export: one device pass); into ``out``
+        when given (e.g. state_buffer(what)), else into a new array."""
+        n = self.state_size(what)
+        if out is None:
+            out = np.empty(n, np.float32)
+        if out.dtype != np.float32 or out.shape != (n,) or not out.flags.c_contiguous:
+            raise ValueError(f"state_export: out must be a contiguous float32 array of {n} elements")
+        _check(lib().rle_state_export(self.h, what, _fp(out), n))
+        return out
+
+    def state_import(self, blob, what=STATE_ALL):
+        blob = _f32(blob).ravel()
+        _check(lib().rle_state_import(self.h, what, _fp(blob), blob.size))
+
+    def copy_nets_from(self, other: "Engine"):
+        """Every network's parameters of ``other`` (rle_copy_nets: device to device, also across two GPUs)."""
+        _check(lib().rle_copy_nets(self.h, other.h))
 
     def counters(self):
         out = np.zeros(6, np.int64)

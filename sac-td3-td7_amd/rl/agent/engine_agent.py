@@ -12,12 +12,14 @@ There is no CPU path: constructing an agent without the HIP library raises.
 
 from __future__ import annotations
 
+import copy
 import math
 
 import numpy as np
 
 from rl import _engine as E
 from rl.agent.abc import Agent
+from rl.agent.state_blob import blob_to_dict, covers, dict_to_blob
 from rl.nn.layout import AGENT_COPIES, AGENT_NETS, init_agent, layers
 from rl.replay_memory.base import BaseReplayMemory, DeviceBatch, _device_index
 from rl.sampler import Sampler
@@ -98,12 +100,20 @@ class EngineAgent(Agent, Sampler):
         return self.engine.cfg.batch
 
     def _rebuild(self, batch=None, device=None):
-        st = self._export()
-        if device is not None:
+        """A fresh engine with this one's whole state.  On the same GPU the state goes device to
+        device (rle_copy_state); to another GPU through one exported blob."""
+        batch = self.batch_size if batch is None else batch
+        old = self.engine
+        if device is None or device == self._device:
+            self.engine = self._new_engine(batch)
+            self.engine.copy_state_from(old)
+            old.close()
+        else:
+            st = self._export()
             self._device = device
-        self.engine.close()
-        self.engine = self._new_engine(self.batch_size if batch is None else batch)
-        self._import(st)
+            old.close()
+            self.engine = self._new_engine(batch)
+            self._import(st)
         self._replay = None
 
     def _prepare(self, replay: BaseReplayMemory, batch: int):
@@ -137,28 +147,45 @@ class EngineAgent(Agent, Sampler):
                     out.append((copy, names))
         return out
 
-    def _export(self):
+    def _export(self, what=E.STATE_ALL, reuse=False):
+        """The engine's state as the nested dict the agents pickle.  Every parameter and Adam moment
+        comes from ONE exported blob (rle_state_export: one pack launch, one copy), cut by its table
+        of contents; the arrays are views of that blob.  ``what`` = STATE_PARAMS: the networks only.
+        ``reuse``: the blob is the engine's reusable host array, valid until the next such export (for a
+        pickler, which serialises the arrays at once: no 24 MB array is allocated and freed per save)."""
         e = self.engine
-        params = {net: {n: e.get_param(net, n, shp) for n, shp in names} for net, names in self._param_names()}
-        adam = {}
-        for net, names in self._param_names():
-            if net in self.OPTIM_NETS:
-                adam[net] = {n: (e.get_adam(net, n, 0, shp), e.get_adam(net, n, 1, shp)) for n, shp in names}
+        names = self._param_names()
+        shapes = {(net, n): shp for net, ns in names for n, shp in ns}
+        blob = e.state_export(what, e.state_buffer(what) if reuse else None)
+        cut = blob_to_dict(e.state_toc(what), blob, shapes)
+        params = {net: {n: cut["params"][net][n] for n, _ in ns} for net, ns in names}
         if self.ALG == "sac":
-            params["tmp"] = {"log_alpha": e.get_param("tmp", "log_alpha")}
-            adam["tmp"] = {"log_alpha": (e.get_adam("tmp", "log_alpha", 0), e.get_adam("tmp", "log_alpha", 1))}
+            params["tmp"] = cut["params"]["tmp"]
+        if what == E.STATE_PARAMS:
+            return {"params": params}
+        adam = {net: {n: cut["adam"][net][n] for n, _ in ns} for net, ns in names if net in self.OPTIM_NETS}
+        if self.ALG == "sac":
+            adam["tmp"] = cut["adam"]["tmp"]
         return {"params": params, "adam": adam, "counters": e.counters(), "vbounds": e.value_bounds(),
                 "act_counter": e.act_counter()}
 
     def _import(self, st):
+        """The reverse.  A dict with every network (and every moment, when it has "adam") goes in as
+        one blob (rle_state_import); a partial one (load_params of some nets) tensor by tensor."""
         e = self.engine
-        for net, d in st["params"].items():
-            for n, v in d.items():
-                e.set_param(net, n, np.asarray(v, np.float32))
-        for net, d in st.get("adam", {}).items():
-            for n, (m, v) in d.items():
-                e.set_adam(net, n, 0, m)
-                e.set_adam(net, n, 1, v)
+        what = E.STATE_ALL if "adam" in st else E.STATE_PARAMS
+        toc = e.state_toc(what)
+        if covers(toc, st):
+            with E.state_scratch(e.state_size(what)) as buf:
+                e.state_import(dict_to_blob(toc, st, buf), what)
+        else:
+            for net, d in st["params"].items():
+                for n, v in d.items():
+                    e.set_param(net, n, np.asarray(v, np.float32))
+            for net, d in st.get("adam", {}).items():
+                for n, (m, v) in d.items():
+                    e.set_adam(net, n, 0, m)
+                    e.set_adam(net, n, 1, v)
         if "counters" in st:
             e.set_counters(st["counters"])
         if "vbounds" in st:
@@ -168,14 +195,16 @@ class EngineAgent(Agent, Sampler):
 
     def state_dict(self):
         """{net: {param name: ndarray}} in the reference's state_dict naming."""
-        return self._export()["params"]
+        return self._export(E.STATE_PARAMS)["params"]
 
     def load_params(self, params):
         self._import({"params": params})
 
     def __getstate__(self):
         d = {k: v for k, v in self.__dict__.items() if k not in ("engine", "_replay")}
-        d["_engine_state"] = self._export()
+        # (the arrays are views of the engine's reusable export array: serialise them before the next
+        # __getstate__ of this agent, as pickle does)
+        d["_engine_state"] = self._export(reuse=True)
         d["_batch"] = self.batch_size
         return d
 
@@ -186,6 +215,20 @@ class EngineAgent(Agent, Sampler):
         self._replay = None
         self.engine = self._new_engine(batch)
         self._import(st)
+
+    def __deepcopy__(self, memo):
+        """copy.deepcopy(agent) (run_w_checkpoint.py:72): the host attributes, and a new engine whose
+        state comes device to device (rle_copy_state) -- what pickle.loads(pickle.dumps(agent)) gives,
+        without the host trip.  Like a pickle, the copy is bound to no replay."""
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            if k not in ("engine", "_replay", "_host_ring"):  # (the ring of host batches is rebuilt on demand)
+                new.__dict__[k] = copy.deepcopy(v, memo)
+        new._replay = None
+        new.engine = new._new_engine(self.batch_size)
+        new.engine.copy_state_from(self.engine)
+        return new
 
     def to(self, device):
         """td7.py:101-112: move to a device.  'cpu' is accepted as a no-op (pickling exports
@@ -201,9 +244,7 @@ class EngineAgent(Agent, Sampler):
         optimiser state, counters or SAC temperature)."""
         if type(agent) is not type(self):
             raise TypeError("load_state_dict needs an agent of the same class")
-        for net, names in self._param_names():
-            for n, _ in names:
-                self.engine.set_param(net, n, agent.engine.get_param(net, n))
+        self.engine.copy_nets_from(agent.engine)  # (rle_copy_nets: device to device, a peer copy across GPUs)
         return self
 
     @property
