@@ -61,6 +61,20 @@ typedef struct rle_config {
      extended kernel instance without RLE_FUSE_PRELAYER, PRE, TWOSTAGE and SACPRE (and, for identity critics, without
      QDOT and HEADDX). */
   int act_actor, act_critic, act_encoder;
+  /* TD7 offline mode (the paper's behaviour-cloning term; the reference names it, rl/cli.py:110-123, and does
+     not implement it): on policy steps the actor objective is
+       -mean(cat Q) + bc_lambda * mean|cat Q|.detach() * mse(pi(s), a)      (a: the batch's stored action).
+     0 = online: the programs are the online ones, op for op.  > 0 (the paper: 0.1): every program with a policy
+     step gains two forward GEMMs that store the per-row q of the policy pass (EPI_QDOT partials, beside the
+     q-head GEMMs), two small ops off the chain (OP_BC: the mse and lmbda 2 (pi - a) / (B A) once the actor
+     output exists; q_abs and q_abs I a level after the partials) and one reduction segment of r16(A) rows in
+     the action-gradient GEMM, which adds dL_bc / d pi ahead of tanh'.  The in-tile recomputation of that
+     gradient (RLE_FUSE_PRE) takes the same extra segment, so no fusion is dropped and the policy step keeps
+     its level count.  The info row gains train/bc (the mse) and train/q_abs after
+     train/policy (NaN on other steps).  The parameter layout does not change: rle_copy_state, rle_copy_nets
+     and rle_state_* work between engines whose bc_lambda differ.  Negative, NaN, or > 0 with another
+     algorithm: RLE_EINVAL. */
+  float bc_lambda;
 } rle_config;
 #define RLE_MAX_HIDDEN 6
 #define RLE_ACT_DEFAULT 0

@@ -949,6 +949,7 @@ static void op_accesses(const Op& op, std::vector<Access>& v) {
         acc_bytes(v, a.la_t, 8, 1, "la_t");
       }
       if (a.sac_scratch) acc_bytes(v, a.sac_scratch, 8, a.mode == 1, "sac scratch");
+      if (info && a.bcs) acc_bytes(v, a.bcs, 4, 0, "bc q_abs");
       break;
     }
     case OP_POLYAK:
@@ -982,6 +983,23 @@ static void op_accesses(const Op& op, std::vector<Access>& v) {
         acc_bytes(v, c.adam_bc2s, (c.la_t ? 4 : 3) * 4, 1, "adam bc2s");
         if (c.la_t) acc_bytes(v, c.la_t, 8, 0, "la_t");
       }
+      break;
+    }
+    case OP_BC: {
+      const BcArgs& b = op.bc;
+      if (b.mode == 0) {
+        acc_whole(v, b.pi.n, 0, "bc pi");
+        acc_whole(v, b.a.n, 0, "bc a");
+        acc_whole(v, b.e.n, 1, "bc e");
+        acc_bytes(v, b.part, (long long)((b.nvalid + 15) / 16) * 4, 1, "bc part");
+        break;
+      }
+      for (int n = 0; n < 2; ++n) {
+        acc_bytes(v, b.qp[n], (long long)b.qp_n[n] * b.qp_ld * 4, 0, "bc qp");
+        acc_bytes(v, b.qb[n], 4, 0, "bc b3");
+      }
+      acc_whole(v, b.eye.t, 1, "bc eye");
+      acc_bytes(v, b.out, 4, 1, "bc q_abs");
       break;
     }
     case OP_FOLDBIAS: {
@@ -2477,18 +2495,24 @@ struct Engine {
     int roff = 0;
     for (size_t t = 0; t < terms.size(); ++t) {
       const DxTerm& tm = terms[t];
-      REQUIRE(tm.L && tm.dz.m.n && tm.col0 % 16 == 0, "pre: dx term layout");
-      p.A.seg[t] = seg_n(tm.dz, roff, roff + tm.L->out);
+      REQUIRE(tm.dz.m.n && tm.col0 % 16 == 0 && (tm.L || (tm.wv && tm.wv->m.t)), "pre: dx term layout");
+      const int wout = tm.L ? tm.L->out : tm.wv->rows;
+      p.A.seg[t] = seg_n(tm.dz, roff, roff + wout);
       Seg b{};
-      b.p = P + tm.L->wt_off + (size_t)(tm.col0 / 16) * tm.L->rb * 256;
-      b.xs = tm.L->rb;
+      if (tm.L) {
+        b.p = P + tm.L->wt_off + (size_t)(tm.col0 / 16) * tm.L->rb * 256;
+        b.xs = tm.L->rb;
+      } else {  // (a derived [out][in] matrix, as dx() takes it)
+        b.p = tm.wv->m.t + (size_t)(tm.col0 / 16) * tm.wv->m.rbs * 256;
+        b.xs = tm.wv->m.rbs;
+      }
       b.x1 = ncols;
       b.r0 = roff;
-      b.r1 = roff + tm.L->out;
+      b.r1 = roff + wout;
       p.B.seg[t] = b;
-      roff += r16(tm.L->out);
+      roff += r16(wout);
       u.rd.push_back(tm.dz.id);
-      u.rd.push_back(tm.L->res);
+      u.rd.push_back(tm.L ? tm.L->res : tm.wv->id);
     }
     p.A.nseg = p.B.nseg = (int)terms.size();
     p.N = ncols;
@@ -2574,7 +2598,7 @@ struct Engine {
     }
     float* qpart = nullptr;
     if (qdot) {  // EPI_QDOT: row partials of the H -> 1 layer qdot applied to this output
-      REQUIRE(!normed && qdot->out == 1 && qdot->K == L.out && (act == ACT_ELU || act == ACT_RELU),
+      REQUIRE(!normed && qdot->out == 1 && qdot->K == L.out && (act == ACT_ELU || act == ACT_RELU || act == ACT_NONE),
               "fwd: q-dot partial layout");
       qpart = mem.make<float>((size_t)tiles_n * M);
       out.qd = qpart;
@@ -3506,6 +3530,62 @@ struct Engine {
                             &nt, n ? ploss_id2 : ploss_id);
         ploss_n += nt;
       }
+      // ---- offline (rle_config bc_lambda): + lmbda * mean|cat Q|.detach() * mse(pi(s), a).  dL/dq stays
+      // -1/(2B) (q_abs is detached), so the q-heads above are the online ones.  The per-row q for q_abs: the
+      // same layers once more with the EPI_QDOT epilogue, beside the q-heads (same level, nothing waits for
+      // them but OP_BC); OP_BC a level later forms q_abs, bc and e = dL_bc / d pi, which the action gradient
+      // below reads several levels on.
+      View bc_e, bc_eye;
+      bc_s = nullptr;
+      if (offline()) {
+        REQUIRE(A <= kThreads && a_pi.m.n && act_in.m.n, "bc: operand layout");
+        // (mode 0: needs the actor output alone, so it runs many levels before the action gradient)
+        bc_e = buf(B, A, true, false);
+        bc_part_n = cdiv(Bv, 16);
+        bc_part = mem.make<float>((size_t)bc_part_n);
+        bc_part_id = next_id++;
+        {
+          Op op{};
+          op.kind = OP_BC;
+          BcArgs& b = op.bc;
+          b.mode = 0;
+          b.nvalid = Bv;
+          b.A = A;
+          b.lambda = cfg.bc_lambda;
+          b.pi = a_pi.m;
+          b.a = act_in.m;
+          b.e = bc_e.m;
+          b.part = bc_part;
+          op.wg_count = bc_part_n;
+          pg.add(op, {a_pi.id, act_in.id}, {bc_e.id, bc_part_id});
+        }
+        View pq[2];
+        out_t = false;
+        for (int n = 0; n < 2; ++n)
+          pq[n] = fwd(pg, q[n]->layers[2], {{p1[n]}}, B, actC, nullptr, false, nullptr, 0, nullptr, nullptr, nullptr,
+                      &q[n]->layers[3]);
+        out_t = true;
+        bc_eye = buf(A, A, false, true);
+        bc_s = mem.make<float>(4);
+        bc_s_id = next_id++;
+        Op op{};
+        op.kind = OP_BC;
+        BcArgs& b = op.bc;
+        b.mode = 1;
+        for (int n = 0; n < 2; ++n) {
+          b.qp[n] = pq[n].qd;
+          b.qp_n[n] = pq[n].qd_n;
+          b.qb[n] = bias(q[n]->layers[3]);
+        }
+        REQUIRE(pq[0].qd_ld == pq[1].qd_ld, "bc: q partial layout");
+        b.qp_ld = pq[0].qd_ld;
+        b.nvalid = Bv;
+        b.A = A;
+        b.eye = bc_eye.m;
+        b.out = bc_s;
+        op.wg_count = 1;
+        pg.add(op, {pq[0].qd_id, pq[1].qd_id, q[0]->layers[3].res, q[1]->layers[3].res}, {bc_eye.id, bc_s_id});
+      }
       View dzp1[2], dxp01[2];
       out_t = false;  // (no weight gradient of the critics or the fixed encoder in the policy pass)
       for (int n = 0; n < 2; ++n) {
@@ -3532,8 +3612,11 @@ struct Engine {
       View dpa1 = dx(pg, {{dpa2, &fe.layers[4], 0}}, H, B, actE, &pa1z);
       out_t = true;
       // d action = sum of three paths, then tanh' (actor output)
-      const std::vector<DxTerm> t3{
+      std::vector<DxTerm> t3{
           {dxp01[0], &q[0]->layers[0], Sp}, {dxp01[1], &q[1]->layers[0], Sp}, {dpa1, &fe.layers[3], Zp}};
+      // (offline: e0 x (q_abs I), the behaviour-cloning gradient wrt pi, one more reduction segment ahead of
+      // tanh' -- in the in-tile recomputation below as well, so RLE_FUSE_PRE stays)
+      if (offline()) t3.push_back({bc_e, nullptr, 0, &bc_eye});
       View dl3 = dx(pg, t3, A, B, ACT_TANH, &a_pi);
       const PreUse p3 = prea ? pre_actor_dx(t3, A, a_pi, 0) : PreUse{};  // dl2 recomputes dl3 in-tile
       // input-grads through a layer are emitted BEFORE its Adam update so the
@@ -3570,11 +3653,31 @@ struct Engine {
       rd.push_back(ploss_id);
       rd.push_back(ploss_id2);
     }
+    if (offline()) {  // info row [encoder, q_fn, policy, bc, q_abs]
+      a.ninfo = 5;
+      if (policy) {
+        a.kind[2] = INFO_SUM_BC;
+        a.bcs = bc_s;
+        a.bc_lambda = cfg.bc_lambda;
+        info_sum(a, 3, bc_part, bc_part_n, 1, 1.f / ((float)Bv * (float)A));
+        info_sum(a, 4, bc_s, 1, 1, 1.f);
+        rd.push_back(bc_s_id);
+        rd.push_back(bc_part_id);
+      } else {
+        a.kind[3] = a.kind[4] = INFO_NAN;
+      }
+    }
     std::vector<int> cn{CNT_ADAM_Q, CNT_ADAM_ENC, 3, CNT_RNG, CNT_TAPE};
     if (policy) cn.push_back(CNT_ADAM_PI);
     add_step_end(pg, op, rd, cn);
   }
   int loss_id_enc = -1, qloss_id = -1, ploss_id = -1, ploss_id2 = -1, ploss_n = 0;
+  // TD7 offline mode (rle_config bc_lambda > 0): OP_BC's outputs of the program being built -- q_abs, and the
+  // row blocks' sums of (pi - a)^2
+  bool offline() const { return algo == RLE_TD7 && cfg.bc_lambda > 0.f; }
+  float* bc_s = nullptr;
+  float* bc_part = nullptr;
+  int bc_s_id = -1, bc_part_id = -1, bc_part_n = 0;
 
   // Upper bound on the tiles of a fwd_qhead GEMM over B rows (its loss partial slots).
   int qhead_tiles(const Layer& L) const { return cdiv(B, kTileM) * cdiv(L.out, kTileM); }
@@ -4240,7 +4343,7 @@ struct Engine {
     }
     static const char* kname[] = {"?", "gemm", "normbwd", "sreduce", "sgather", "head", "prio",
                                   "sacfwd", "sacbwd", "end", "polyak", "copy", "maxred", "ctrl", "noise",
-                                  "foldbias"};
+                                  "foldbias", "bc"};
     static const bool traffic = [] {
       const char* e = std::getenv("RLE_TRAFFIC");
       return e && e[0] == '1';
@@ -5290,6 +5393,8 @@ int rle_create(const rle_config* cfg, rle_engine** out) {
     for (int a : {cfg->act_actor, cfg->act_critic, cfg->act_encoder})
       REQUIRE(a >= RLE_ACT_DEFAULT && a <= RLE_ACT_IDENTITY, "create: activation must be an RLE_ACT_* code");
     REQUIRE(cfg->algo == RLE_TD7 || cfg->act_encoder == RLE_ACT_DEFAULT, "create: act_encoder is TD7's (SALEEncoder)");
+    REQUIRE(cfg->bc_lambda >= 0.f && std::isfinite(cfg->bc_lambda), "create: bc_lambda must be a finite value >= 0");
+    REQUIRE(cfg->bc_lambda == 0.f || cfg->algo == RLE_TD7, "create: bc_lambda (offline mode) is TD7's");
     HIPCHK(hipSetDevice(cfg->device));
     auto h = std::make_unique<rle_engine>();
     h->e = std::make_unique<Engine>();

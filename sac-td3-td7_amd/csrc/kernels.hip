@@ -2936,6 +2936,9 @@ __device__ __forceinline__ void op_step_end(const CAS StepEndArgs& a, float* sme
   const bool la_pre = sac_tmp && a.adam_step;
   const float la_bx = la_pre ? G(a.adam_step)[3] : 0.f, la_by = la_pre ? G(a.adam_bc2s)[3] : 0.f;
   const float scr_alpha = scr ? G(a.sac_scratch)[0] : 0.f, scr_slp = scr ? G(a.sac_scratch)[1] : 0.f;
+  // (TD7 offline: OP_BC's q_abs and bc for the policy objective's second term)
+  const bool bcv = w0 && a.bcs && mode != 1;
+  const float bc_q = bcv ? G(a.bcs)[0] : 0.f;
   FINE_MARK(0);
   // sum list: j < ninfo -> info k (if summed); kInfoMax -> logpi; kInfoMax+1+q -> gsq tensor q
   auto sum_src = [&](int j, const float*& p, int& n, int& stride) {
@@ -2943,7 +2946,7 @@ __device__ __forceinline__ void op_step_end(const CAS StepEndArgs& a, float* sme
     n = 0;
     stride = 1;
     if (j < kInfoMax) {
-      if (j < a.ninfo && (a.kind[j] == INFO_SUM || a.kind[j] == INFO_SAC_POL)) {
+      if (j < a.ninfo && (a.kind[j] == INFO_SUM || a.kind[j] == INFO_SAC_POL || a.kind[j] == INFO_SUM_BC)) {
         p = a.part[j];
         n = a.npart[j];
         stride = a.stride[j];
@@ -3031,6 +3034,7 @@ __device__ __forceinline__ void op_step_end(const CAS StepEndArgs& a, float* sme
       case INFO_SAC_POL: v = v * a.scale[k] + tmp_obj; break;
       case INFO_SAC_TMPL: v = tmp_obj; break;
       case INFO_SAC_ENT: v = -slp * a.inv_b; break;
+      case INFO_SUM_BC: v = v * a.scale[k] + (a.bc_lambda * bc_q) * (vals[k + 1] * a.scale[k + 1]); break;
     }
     if (tid == k) mine = v;
   }
@@ -3115,6 +3119,39 @@ __device__ __forceinline__ void op_foldbias(const CAS FoldBiasArgs& f) {
     for (int z = 0; z < f.H; ++z) acc += f.wn[nidx(f.cbn, o, f.col0 + z)] * f.bin[z];
     f.bout[o] = f.bbase[o] + acc;
   }
+}
+
+// ---------------------------------------------------------------- behaviour-cloning term (TD7 offline)
+// (ops.h BcArgs; off the step's chain.  Small loops on purpose: a one-workgroup op's cold code is fetched at L2
+// latency, and an unrolled version of this op was the longest of its level)
+__device__ __forceinline__ void op_bc(const CAS BcArgs& b, int t, float* smem) {
+  const int tid = threadIdx.x;
+  const int B = b.nvalid, A = b.A;
+  if (b.mode == 0) {  // row block t: e0 and the block's sum of squares
+    const int r0 = t * 16, n = 16 * A;
+    const float c = (b.lambda * 2.f) / ((float)B * (float)A), inv_a = 1.f / (float)A;
+    float d2 = 0.f;
+    for (int i = tid; i < n; i += kThreads) {
+      const int rr = (int)(((float)i + 0.5f) * inv_a), j = i - rr * A, r = r0 + rr;
+      if (r >= B) continue;
+      const float d = G(b.pi.n)[nidx(b.pi.cbn, r, j)] - G(b.a.n)[nidx(b.a.cbn, r, j)];
+      d2 += d * d;
+      GW(b.e.n)[nidx(b.e.cbn, r, j)] = c * d;
+    }
+    d2 = wg_sum(d2, smem);
+    if (tid == 0) GW(b.part)[t] = d2;
+    return;
+  }
+  const float b0 = G(b.qb[0])[0], b1 = G(b.qb[1])[0];
+  float qa = 0.f;
+  for (int r = tid; r < B; r += kThreads) {  // (a row's partials in column-tile order, 16 loads at a time)
+    const float q0 = norm_mean_i(b.qp[0], b.qp_ld, r, b.qp_n[0], 1);
+    const float q1 = norm_mean_i(b.qp[1], b.qp_ld, r, b.qp_n[1], 1);
+    qa += fabsf(q0 + b0) + fabsf(q1 + b1);
+  }
+  const float q_abs = wg_sum(qa, smem) / (2.f * (float)B);
+  if (tid == 0) GW(b.out)[0] = q_abs;
+  if (tid < A) GW(b.eye.t)[tidx(b.eye.rbs, tid, tid)] = q_abs;
 }
 
 // ---------------------------------------------------------------- dispatch
@@ -3218,6 +3255,8 @@ __global__ __launch_bounds__(kThreads, RLE_WAVES) void rle_level(unsigned e0, un
     RLE_OP(OP_CTRL, op_ctrl<ks_family(KS) != KS_TD7>(op.ctrl))
     RLE_OP(OP_NOISE, op_noise(op.sample, t))
     RLE_OP(OP_FOLDBIAS, op_foldbias(op.fb))
+    // (kinds past 15, ops.h OpKind: low bits 0, kind >> 4 in the variant field; the TD7 family's instances)
+    RLE_OP(0, if (ks_family(KS) != KS_MLP && vid == (OP_BC >> 4)) op_bc(op.bc, t, smem))
 #undef RLE_OP
     default: break;
   }
@@ -3749,8 +3788,8 @@ hipError_t launch_level(const Op* d_ops, const Op* h_ops, int nops, int nwg, hip
     for (int q = 0; q < kLevelOps; ++q) {
       if (q < n) {
         const Op& o = h_ops[q0 + q];
-        const unsigned vid = o.kind == OP_GEMM ? (unsigned)o.gemm.vid : 0u;
-        la.entry[q] = (unsigned)(o.wg_begin - w0) | ((unsigned)o.kind << 16) | (vid << 20);
+        const unsigned vid = o.kind == OP_GEMM ? (unsigned)o.gemm.vid : (unsigned)o.kind >> 4;
+        la.entry[q] = (unsigned)(o.wg_begin - w0) | (((unsigned)o.kind & 0xfu) << 16) | (vid << 20);
       } else {
         la.entry[q] = 0xffffu;
       }

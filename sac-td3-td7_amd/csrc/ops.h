@@ -31,6 +31,9 @@ enum OpKind : int {
   OP_CTRL = 13,
   OP_NOISE = 14,        // target-smoothing / rsample noise of the batch (SampleArgs)
   OP_FOLDBIAS = 15,     // bias of a folded weight block (FoldBiasArgs)
+  // Kinds past 15: a level-launch entry keeps a kind's low four bits in bits 16-19 (0 for these) and, for a
+  // non-GEMM op, kind >> 4 in the variant field (LevelArgs::entry), so every earlier entry is unchanged.
+  OP_BC = 16,           // TD7 offline: the behaviour-cloning term's scalars and action-gradient operand (BcArgs)
 };
 
 // ---------------------------------------------------------------- tensor images
@@ -150,7 +153,8 @@ static_assert(gemm_vid(2, 8, 15, 1, 3) < 2048, "GEMM variant ids fit 11 bits");
 // pre-GEMM, 5 SAC raw head pre-GEMM) and the kernel sets that hold it (bit 0: TD7, bit 1: TD3 / SAC; the
 // extended instance holds all).  kernels.hip op_gemm dispatches exactly these, and the engine refuses a
 // program with an op whose id is not in its kernel set.  (sets 0: the extended instance only -- the TD7 policy
-// pass's q-head under a non-default critic activation, rle_config act_critic)
+// pass's q-head under a non-default critic activation, rle_config act_critic, and the offline policy pass's
+// q row partials under identity critics, rle_config bc_lambda)
 #define RLE_GEMM_VARIANTS(X)                        \
   X(GEMM_FWD, EPI_STORE, ACT_NONE, 0, 0, 0, 3)      \
   X(GEMM_FWD, EPI_STORE, ACT_NONE, 1, 0, 0, 1)      \
@@ -168,6 +172,7 @@ static_assert(gemm_vid(2, 8, 15, 1, 3) < 2048, "GEMM variant ids fit 11 bits");
   X(GEMM_FWD, EPI_ACT, ACT_TANH, 0, 0, 0, 3)        \
   X(GEMM_FWD, EPI_QDOT, ACT_ELU, 0, 0, 0, 1)        \
   X(GEMM_FWD, EPI_QDOT, ACT_RELU, 0, 0, 0, 2)       \
+  X(GEMM_FWD, EPI_QDOT, ACT_NONE, 0, 0, 0, 0)       \
   X(GEMM_DX, EPI_STORE, ACT_NONE, 0, 0, 0, 3)       \
   X(GEMM_DX, EPI_STORE, ACT_RELU, 0, 0, 0, 3)       \
   X(GEMM_DX, EPI_STORE, ACT_ELU, 0, 0, 0, 3)        \
@@ -490,6 +495,8 @@ struct StepEndArgs {
   // written by mode 1 for mode 2 (autotuned SAC temperature)
   int mode;
   float* sac_scratch;
+  // TD7 offline (INFO_SUM_BC): OP_BC's q_abs [1] and lmbda (bc is the next info column's own sum)
+  const float* bcs; float bc_lambda;
 };
 
 enum InfoKind : int {
@@ -501,6 +508,7 @@ enum InfoKind : int {
   INFO_SAC_POL = 5,   // policy_obj + tmp_obj
   INFO_SAC_TMPL = 6,  // tmp_obj
   INFO_SAC_ENT = 7,   // -mean(logpi)
+  INFO_SUM_BC = 8,    // scale * sum + bc_lambda * bcs[0] * (info k + 1: scale * sum) (TD7 offline train/policy)
 };
 
 // Bias of a layer whose input block [col0, col0 + H) is fed by a linear layer folded
@@ -512,6 +520,34 @@ struct FoldBiasArgs {
   const float* bin;                    // bias of the folded-in layer [H]
   const float* bbase;                  // bias of the consuming layer [H]
   float* bout;                         // [H]
+};
+
+// TD7 offline policy step (rle_config bc_lambda > 0): the behaviour-cloning term of the actor objective,
+//   L = -mean(cat Q) + lmbda * mean|cat Q|.detach() * mse(pi, a)
+// over rows < nvalid and columns < A, in two small ops off the step's chain:
+//   mode 0 (once the actor output pi exists, one workgroup per 16-row block rb; nothing but the action gradient,
+//     many levels on, waits for it):
+//       e0_ij    = lmbda * 2 (pi_ij - a_ij) / (nvalid A)   (N image; padded rows and columns stay zero)
+//       part[rb] = sum_ij (pi_ij - a_ij)^2 of the block    (bc = sum_rb part[rb] / (nvalid A), formed by the step end)
+//   mode 1 (a level after the policy pass's EPI_QDOT row partials of q - b3, as HeadArgs::qp; one workgroup):
+//       out[0] = q_abs = sum_i (|q1_i| + |q2_i|) / (2 nvalid)
+//       eye    = q_abs * I  ([A][A], T image)
+// dL_bc / d pi = e0 x (q_abs I): the action-gradient GEMM takes e0 and eye as one more reduction segment, ahead
+// of tanh'.  Summation order: mode 0 thread t of block rb adds its elements t, t + 256, ... of the block's
+// [16][A] (row-major), mode 1 thread t the rows t, t + 256, ... (a row's partials in column-tile order); then
+// wg_sum.  Fixed by B, A and the partials' tile width alone, whatever the launch order.
+struct BcArgs {
+  int mode;
+  int nvalid, A;
+  float lambda;
+  Mat pi, a;             // mode 0: N images [B][Ap]
+  Mat e;                 // mode 0: N image [B][Ap] out
+  float* part;           // mode 0: [row blocks] out
+  const float* qp[2];    // mode 1: [qp_n][qp_ld] row partials of q - b3
+  const float* qb[2];    // mode 1: b3 [1]
+  int qp_n[2], qp_ld;
+  Mat eye;               // mode 1: T image [A][A] out (the diagonal; the rest stays zero)
+  float* out;            // mode 1: [1]
 };
 
 struct FlatArgs {   // POLYAK / COPY / MAXRED
@@ -546,13 +582,15 @@ struct Op {
     FlatArgs flat;
     CtrlArgs ctrl;
     FoldBiasArgs fb;
+    BcArgs bc;
   };
 };
 // kernels.hip gemm_v touches the descriptor's 64-byte lines by fixed offsets from &gemm (its
 // TL_* lists): ops are 64-byte aligned in their tables and the GEMM fields sit at these offsets.
 static_assert(sizeof(HeadArgs) <= sizeof(PreArgs), "GemmArgs: the fused head shares the pre-GEMM's fields");
 static_assert(sizeof(Op) % 64 == 0 && offsetof(Op, gemm) == 16, "Op layout (descriptor line touches)");
-static_assert(16 + sizeof(HeadArgs) <= 8 * 64 && 16 + sizeof(StepEndArgs) <= 8 * 64 && 16 + sizeof(SampleArgs) <= 8 * 64,
+static_assert(16 + sizeof(HeadArgs) <= 8 * 64 && 16 + sizeof(StepEndArgs) <= 8 * 64 && 16 + sizeof(SampleArgs) <= 8 * 64 &&
+                  16 + sizeof(BcArgs) <= 8 * 64,
               "rle_level touches 8 descriptor lines of a non-GEMM op");
 static_assert(offsetof(GemmArgs, A) == 0xb0 && offsetof(GemmArgs, B) == 0x1a0 && offsetof(GemmArgs, out) == 0x290 &&
                   offsetof(GemmArgs, noise) == 0x2f0 && offsetof(GemmArgs, nbx) == 0x370 &&
@@ -608,8 +646,9 @@ constexpr int kLevelOps = 12;  // ops per launch: the op table is 12 preloaded k
 struct LevelArgs {
   const Op* ops;
   unsigned long long* trace;  // optional phase timestamps [wg][4] (s_memrealtime, 100 MHz)
-  // op q: first workgroup (bits 0-15; 0xffff past the last op) | kind << 16 (4 bits) | GEMM
-  // variant id << 20 (GemmArgs::vid: the variant is chosen before any descriptor load)
+  // op q: first workgroup (bits 0-15; 0xffff past the last op) | (kind & 15) << 16 | GEMM
+  // variant id << 20 (GemmArgs::vid: the variant is chosen before any descriptor load; a non-GEMM
+  // op: kind >> 4, 0 for every kind up to 15)
   unsigned entry[kLevelOps];
 };
 constexpr int kMaxLevelWG = 0xfffe;  // workgroups per launch (16-bit entry field)

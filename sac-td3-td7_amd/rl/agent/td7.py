@@ -14,18 +14,27 @@ class TD7(EngineAgent):
     Same constructor arguments as the reference (td7.py:34-48) plus ``hidden``
     (hdim = zs_dim), ``batch_size`` (the captured step's B; train_ops with another
     B rebuilds the step graphs), ``seed`` (weight init + Philox stream) and ``device``.
+
+    ``offline=True`` trains from a fixed dataset (the TD7 paper's offline mode, which the reference names
+    and does not implement): on policy steps the actor objective gains the behaviour-cloning term
+    ``lmbda * mean|Q|.detach() * mse(pi(s), a)`` (``a``: the batch's stored action), and the info dict
+    two keys, ``train/bc`` (the mse) and ``train/q_abs`` (None on other steps).  ``offline=False``
+    ignores ``lmbda``.
     """
 
     ALG = "td7"
     ALGO = E.RLE_TD7
     OPTIM_NETS = ("encoder", "policy", "q1", "q2")
-    NULLABLE = ("train/policy",)
+    NULLABLE = ("train/policy", "train/bc", "train/q_abs")
+    offline = False  # (class defaults: an agent pickled before the offline mode existed loads as online)
+    lmbda = 0.1
 
     def __init__(self, env_id: str, discount_factor: float = 0.99, policy_lr: float = 3e-4,
                  critic_lr: float = 3e-4, target_update_rate: int = 250, exploration_noise: float = 0.1,
                  target_policy_noise: float = 0.2, noise_clip: float = 0.5, policy_freq: int = 2,
                  use_lap: bool = False, make_nn=None, *, hidden: int = 256, batch_size: int = 256,
-                 seed: int | None = None, device=None, **make_nn_kwargs) -> None:
+                 seed: int | None = None, device=None, offline: bool = False, lmbda: float = 0.1,
+                 **make_nn_kwargs) -> None:
         self.discount_factor = discount_factor
         self.target_update_rate = target_update_rate
         self.target_policy_noise = target_policy_noise
@@ -36,11 +45,17 @@ class TD7(EngineAgent):
         cfg = dict(use_lap=use_lap, discount=discount_factor, policy_lr=policy_lr, critic_lr=critic_lr,
                    target_policy_noise=target_policy_noise, noise_clip=noise_clip, policy_freq=policy_freq,
                    target_update_rate=target_update_rate)
+        self.offline = bool(offline)
+        self.lmbda = float(lmbda)
+        if self.offline:  # (in _cfg: every engine this agent builds -- _rebuild, pickle, deepcopy, to() -- carries it)
+            cfg["bc_lambda"] = self.lmbda
         self._setup(env_id, hidden=hidden, batch_size=batch_size, seed=seed, device=device, make_nn=make_nn,
                     make_nn_kwargs=make_nn_kwargs, cfg=cfg)
 
     def _info_keys(self):
-        return ("train/encoder", "train/q_fn", "train/policy")  # td7.py:302,314,317
+        keys = ("train/encoder", "train/q_fn", "train/policy")  # td7.py:302,314,317
+        bc = getattr(self, "_cfg", {}).get("bc_lambda", 0.0) > 0  # (the engine's offline programs: two more columns)
+        return keys + ("train/bc", "train/q_abs") if bc else keys
 
     @property
     def value_max(self):

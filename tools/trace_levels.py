@@ -1,6 +1,6 @@
 """Per-level phase timing of the TD7 Humanoid step from in-kernel timestamps (GPU box).
 
-RLE_TRACE=1 python tools/trace_levels.py [steps]
+RLE_TRACE=1 python tools/trace_levels.py [steps]        (RLE_TRACE_BC=0.1: TD7's offline programs)
 Phases per workgroup (s_memrealtime, 10 ns ticks): dispatch delay (entry - level's first
 entry), prologue (entry -> main loop), main loop, epilogue (-> exit); the level span is
 first entry -> last exit.
@@ -23,7 +23,9 @@ ALGO = os.environ.get("RLE_TRACE_ALGO", "td7")
 S, A, H, B = (17, 6, 256, 256) if ALGO == "td3" else (376, 17, 256, 256)
 B = int(os.environ.get("RLE_TRACE_BATCH", B))  # (BASELINE config 4: 1024)
 LAP = ALGO == "td7"
-eng = E.Engine(E.make_config({"td7": E.RLE_TD7, "td3": E.RLE_TD3, "sac": E.RLE_SAC}[ALGO], S, A, H, B, use_lap=LAP),
+BC = float(os.environ.get("RLE_TRACE_BC", 0))  # (TD7 offline mode: rle_config bc_lambda)
+eng = E.Engine(E.make_config({"td7": E.RLE_TD7, "td3": E.RLE_TD3, "sac": E.RLE_SAC}[ALGO], S, A, H, B, use_lap=LAP,
+                             bc_lambda=BC),
                E.parse_plan(os.environ.get("RLE_PLAN", "")))  # (RLE_PLAN: the plan to trace, bench.py --plan syntax)
 for net, params in init_agent(ALGO, S, A, H, 1).items():
     for k, v in params.items():
