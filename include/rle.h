@@ -36,8 +36,9 @@ typedef struct rle_engine rle_engine;
 
 typedef struct rle_config {
   int algo;                 /* RLE_TD7 / RLE_TD3 / RLE_SAC */
-  int state_dim, action_dim;
-  int hidden;               /* hidden width (TD7: hdim; TD3/SAC: every hidden layer unless n_hidden is set) */
+  int state_dim, action_dim;  /* 1..1024, 1..128 */
+  int hidden;               /* hidden width, a multiple of 4, <= 512 (TD7: hdim; TD3/SAC: every hidden layer unless
+                               n_hidden is set) */
   int batch;                /* B, 1..1024 (padded to 16 rows inside; the padded rows count in nothing) */
   int use_lap;              /* TD7/TD3: LAP Huber + priority update */
   float discount;           /* td7.py:37 / td3.py:36 / sac.py:30 */
@@ -51,7 +52,7 @@ typedef struct rle_config {
   unsigned long long seed;  /* Philox stream for sampling / noise */
   int device;
   /* Net shapes beyond the defaults (make_nn, td7.py:46-61 / td3.py:44-58 / sac.py:40-52): */
-  int zs_dim;               /* TD7: SALE embedding width (sale.py:23 zs_dim); 0 = hidden.  `hidden` is hdim */
+  int zs_dim;               /* TD7: SALE embedding width (sale.py:23 zs_dim); 0 = hidden; a multiple of 4, <= 512.  `hidden` is hdim */
   int n_hidden;             /* TD3/SAC: hidden layers of make_mlp (mlp.py:10-35), 2..RLE_MAX_HIDDEN; 0 = two
                                layers of `hidden` (mlp.py:45-47) */
   int hidden_sizes[8];      /* TD3/SAC: their widths, input side first (each a multiple of 4, <= 512) */

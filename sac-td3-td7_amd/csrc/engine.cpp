@@ -2598,7 +2598,8 @@ struct Engine {
     }
     float* qpart = nullptr;
     if (qdot) {  // EPI_QDOT: row partials of the H -> 1 layer qdot applied to this output
-      REQUIRE(!normed && qdot->out == 1 && qdot->K == L.out && (act == ACT_ELU || act == ACT_RELU || act == ACT_NONE),
+      // (qdot->K is the padded width: the kernel zeroes the weights of the columns past L.out, j < N)
+      REQUIRE(!normed && qdot->out == 1 && qdot->K == r16(L.out) && (act == ACT_ELU || act == ACT_RELU || act == ACT_NONE),
               "fwd: q-dot partial layout");
       qpart = mem.make<float>((size_t)tiles_n * M);
       out.qd = qpart;

@@ -1015,7 +1015,9 @@ __device__ __forceinline__ f32x4 headdx_reduce(const CAS GemmArgs& g, int i0, in
   if (run) ring_issue(xa, xb, ra, va, rb, vb, n, false);
   float* dqs = smem + 64 + 1024;  // [16] dq of critic hn per tile row (the tabs region)
   float* w3s = dqs + 16;          // [H] critic hn's last-layer weights
-  for (int c = 4 * tid; c < h.H; c += 4 * kThreads) *(float4*)(w3s + c) = ld4g(G(h.w[hn]) + nidx(h.w_cbn, 0, c));
+  // (through the padded width: the DX below reads whole 16-column chunks, and the image's padding is zero)
+  for (int c = 4 * tid; c < ((h.H + 15) & ~15); c += 4 * kThreads)
+    *(float4*)(w3s + c) = ld4g(G(h.w[hn]) + nidx(h.w_cbn, 0, c));
   // q of the twins and (loss heads) of the target twins for the tile's 16 rows from their
   // EPI_QDOT row partials: wave w sums quantity w (0 / 1: q of critic 0 / 1, 2 / 3: the target
   // critics' q), lane l adds partials 16 (l / 16) .. +15 of row l % 16 in order, then the 4 lane
@@ -2712,7 +2714,8 @@ __device__ __forceinline__ void op_sample_gather(const CAS SampleArgs& s, int t,
   // whole float4s, instead of every wave storing its row as four scattered floats per column quad.
   // A/B: TD7 Humanoid +0.4%, SAC Humanoid +0.4%, TD7 B = 1024 +0.8%; rows of <= 64 floats (TD3
   // HalfCheetah) -0.3%: they keep the per-wave stores.)
-  const bool quad = (s.nq & 3) == 0 && s.Sp >= 128;  // (uniform; a partial last quad of queries: per-wave stores)
+  // (Sp <= 512: the four staged rows, 4 (2 Sp + Ap) floats, fit the op's LDS; wider rows take the per-wave stores)
+  const bool quad = (s.nq & 3) == 0 && s.Sp >= 128 && s.Sp <= 512;  // (uniform; a partial last quad of queries: per-wave stores)
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
     const int c = 4 * lane + 256 * p;
@@ -2727,6 +2730,11 @@ __device__ __forceinline__ void op_sample_gather(const CAS SampleArgs& s, int t,
         mat_str4(s.ss, s.B + b, c, v1[p]);
       }
     }
+  }
+  // (rows wider than the two passes above, state_dim 513..1024: their remaining columns, a round trip per pass)
+  for (int c = 4 * lane + 512; c < s.Sp; c += 256) {
+    mat_str4(s.ss, b, c, ld4g(G(s.state) + (size_t)ind * s.Sp + c));
+    mat_str4(s.ss, s.B + b, c, ld4g(G(s.next_state) + (size_t)ind * s.Sp + c));
   }
   if (4 * lane < s.Ap) {
     if (!quad) mat_str4(s.a, b, 4 * lane, va);
