@@ -77,6 +77,30 @@ typedef struct rle_config {
      algorithm: RLE_EINVAL. */
   float bc_lambda;
 } rle_config;
+/* Extension of rle_config.  rle_config itself is frozen (bc_lambda stays its last field); later settings are
+   added here, at the end, and a caller compiled against an older header keeps working: `size` tells the
+   library how much of the struct the caller knows, and every field past it reads as 0. */
+typedef struct rle_config_ext {
+  int size;        /* sizeof(rle_config_ext) as the caller compiled it; fields past it read as 0 */
+  /* TD3 offline mode (TD3+BC, Fujimoto & Gu 2021; the reference does not implement it): on policy steps the
+     actor objective is
+       -lmbda * mean(min(Q1, Q2)) + mse(pi(s), a),   lmbda = bc_alpha / mean|min(Q1, Q2)|.detach()
+     (a: the batch's stored action; every mean over the B valid rows; min(Q1, Q2) is this code base's TD3
+     objective, td3.py:191; no guard for mean|Q| = 0, as in the paper's code: lmbda is then inf).  0 = online: the
+     programs are the online ones, op for op.  > 0 (the paper: 2.5): the backward chain stays the online one
+     (dL/dq = -1/B, so it carries the gradient of L / lmbda); two small ops off the chain (OP_BC: the mse and
+     2 (pi - a) / (B A) once the actor output exists; q_abs, lmbda and (q_abs / bc_alpha) I beside the fused
+     policy head from the policy pass's q row partials, or a level after the standalone head from its |min|
+     partials) feed one more reduction segment of r16(A) rows into the
+     action-gradient GEMM (and its in-tile recomputation, RLE_FUSE_PRE), and the actor's Adam epilogues and
+     the norm/policy partials multiply the accumulated gradient by the device scalar lmbda.  No fusion is
+     dropped; a plain step keeps its level count, a policy step too under the default plan (at most one more
+     with the standalone loss head).  The info row gains train/bc (the mse)
+     and train/lmbda after norm/policy (NaN on other steps).  The parameter layout does not change:
+     rle_copy_state, rle_copy_nets and rle_state_* work between engines whose bc_alpha differ.  Negative, NaN,
+     infinite, > 0 with another algorithm, or a `size` that does not reach the field: RLE_EINVAL. */
+  float bc_alpha;
+} rle_config_ext;
 #define RLE_MAX_HIDDEN 6
 #define RLE_ACT_DEFAULT 0
 #define RLE_ACT_RELU 1
@@ -194,11 +218,25 @@ int rle_replay_set_state(rle_replay* r, long long ptr, long long size, float max
 /* copy.deepcopy(replay) on the device(s): the whole ring, priorities, LAP sums, ptr / size / max_priority of
  * src into dst (same capacity, dims and lap; the two may live on different GPUs).  No host round trip. */
 int rle_replay_copy(rle_replay* dst, rle_replay* src);
+/* Dataset state normalisation on the device (the TD3+BC recipe's; a 1M-row Humanoid ring would otherwise make
+ * a 3 GB host round trip).  Like every replay operation they first wait for the bound engines' enqueued steps. */
+/* Per-feature mean and population std (ddof 0) of `state` over rows [0, size): fp64 accumulation,
+ * two passes (mean, then centred squares), fixed reduction order (per-workgroup partials whose count depends
+ * on size and state_dim alone, added in ascending order); results rounded to fp32.  mean [S], std [S].
+ * NULL pointer: RLE_EINVAL; size == 0: RLE_ESTATE. */
+int rle_replay_state_stats(rle_replay* r, float* mean, float* std);
+/* state and next_state of rows [0, size) <- (x - shift[j]) / scale[j] in fp32, in that order of operations.
+ * The ring's pad columns stay zero, rows at or past size, priorities and LAP sums are untouched, and bound
+ * engines redraw their prefetched batch.  shift [S], scale [S]; a NULL pointer, a non-finite shift, a zero
+ * or non-finite scale: RLE_EINVAL; size == 0: RLE_ESTATE. */
+int rle_replay_normalize_states(rle_replay* r, const float* shift, const float* scale);
 
 /* ---- agent: rl/agent/{td7,td3,sac}.py ------------------------------------- */
 
 /* TD7.__init__ (td7.py:34-87) / TD3.__init__ (td3.py:33-74) / SAC.__init__ (sac.py:27-77). */
 int rle_create(const rle_config* cfg, rle_engine** out);
+/* The same with an extension (NULL: every extension field 0; rle_create is exactly this with NULL). */
+int rle_create_ext(const rle_config* cfg, const rle_config_ext* ext, rle_engine** out);
 int rle_destroy(rle_engine* e);
 /* The default plan (every field "default"); the engine's plan before its first step; the plan in
  * effect (defaults resolved for this engine's algorithm and device). */

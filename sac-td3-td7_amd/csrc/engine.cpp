@@ -52,6 +52,9 @@ hipError_t launch_fill(float* state, float* next_state, float* action, float* re
                        hipStream_t st);
 hipError_t launch_replay_pack(const ReplayPackArgs& a, hipStream_t st);
 hipError_t launch_replay_unpack(const ReplayPackArgs& a, hipStream_t st);
+hipError_t launch_replay_colsum(const ReplayStatArgs& a, hipStream_t st);
+hipError_t launch_replay_colfin(const ReplayStatArgs& a, hipStream_t st);
+hipError_t launch_replay_normalize(const ReplayNormArgs& a, hipStream_t st);
 hipError_t launch_state_pack(const StatePackArgs& a, hipStream_t st);
 hipError_t launch_state_unpack(const StatePackArgs& a, hipStream_t st);
 
@@ -347,9 +350,10 @@ static void gemm_finalize(GemmArgs& g, bool xcd = true) {
   const int act = g.mode == GEMM_FWD ? g.act : (g.mode == GEMM_DX ? g.dact : g.act);
   REQUIRE(g.mode != GEMM_DX || !norm, "gemm: no DX variant with normed operands");
   REQUIRE(g.mode != GEMM_DW || g.epi == EPI_ADAM, "gemm: DW is always fused with Adam");
-  REQUIRE(g.mode != GEMM_DW || act == ACT_NONE || (act == kDwNb && !norm && g.nbx.t && g.nbm.part && g.nbdot &&
-                                                   g.R <= 1024),
-          "gemm: deferred AvgL1Norm backward operands");
+  REQUIRE(g.mode != GEMM_DW || act == ACT_NONE || (act == kDwGs && !norm && g.gscale) ||
+              (act == kDwNb && !norm && g.nbx.t && g.nbm.part && g.nbdot && g.R <= 1024),
+          "gemm: deferred AvgL1Norm backward / gradient scale operands");
+  REQUIRE(g.mode != GEMM_DW || (act == kDwGs) == (g.gscale != nullptr), "gemm: gscale is the kDwGs variant's");
   REQUIRE(g.epi != EPI_NBDOT || (g.mode == GEMM_DX && act == ACT_NONE && g.nbx.t && g.norm_out),
           "gemm: EPI_NBDOT is a plain DX with x and partials");
   REQUIRE(g.epi != EPI_MSE || act == ACT_NONE, "gemm: MSE epilogue takes no activation");
@@ -751,6 +755,7 @@ static void audit_gemm(const GemmArgs& g0) {
   if (g.epi == EPI_ADAM) {  // this step's bias corrections (Ctrl / adamsc1)
     audit_range(g.adam.step, 0, 4, "adam step", g);
     audit_range(g.adam.bc2s, 0, 4, "adam bc2s", g);
+    if (g.gscale) audit_range(g.gscale, 0, 4, "adam gscale", g);
   }
   if (g.has_pre == 2) {  // the fused loss head (kernels.hip headdx_reduce), tile rows i0 .. i0 + 15
     const HeadArgs& h = g.hd;
@@ -949,7 +954,8 @@ static void op_accesses(const Op& op, std::vector<Access>& v) {
         acc_bytes(v, a.la_t, 8, 1, "la_t");
       }
       if (a.sac_scratch) acc_bytes(v, a.sac_scratch, 8, a.mode == 1, "sac scratch");
-      if (info && a.bcs) acc_bytes(v, a.bcs, 4, 0, "bc q_abs");
+      // (offline TD3 reads lmbda too, INFO_SUM_BC3 / INFO_BCS1: bytes [4, 8) of OP_BC's out)
+      if (info && a.bcs) acc_bytes(v, a.bcs, a.kind[1] == INFO_SUM_BC3 ? 8 : 4, 0, "bc q_abs");
       break;
     }
     case OP_POLYAK:
@@ -992,6 +998,21 @@ static void op_accesses(const Op& op, std::vector<Access>& v) {
         acc_whole(v, b.a.n, 0, "bc a");
         acc_whole(v, b.e.n, 1, "bc e");
         acc_bytes(v, b.part, (long long)((b.nvalid + 15) / 16) * 4, 1, "bc part");
+        break;
+      }
+      if (b.mode == 3) {  // (offline TD3 beside the fused head: mode 1's reads, mode 2's writes)
+        for (int n = 0; n < 2; ++n) {
+          acc_bytes(v, b.qp[n], (long long)b.qp_n[n] * b.qp_ld * 4, 0, "bc qp");
+          acc_bytes(v, b.qb[n], 4, 0, "bc b3");
+        }
+        acc_whole(v, b.eye.t, 1, "bc eye");
+        acc_bytes(v, b.out, 8, 1, "bc q_abs lmbda");
+        break;
+      }
+      if (b.mode == 2) {  // (offline TD3: the policy head's loss partials, slot 1 of every group of qp_ld)
+        acc_bytes(v, b.qp[0], ((long long)(b.qp_n[0] - 1) * b.qp_ld + 1) * 4, 0, "bc |min| partials");
+        acc_whole(v, b.eye.t, 1, "bc eye");
+        acc_bytes(v, b.out, 8, 1, "bc q_abs lmbda");
         break;
       }
       for (int n = 0; n < 2; ++n) {
@@ -1721,6 +1742,9 @@ struct Engine {
   // extended instance when the plan asks for its opt-in paths
   int kernel_set() const {
     if (!acts_default) return KS_EXT;  // (the activation variants outside the agent's own set)
+    // (offline TD3: OP_BC modes 2 / 3, the kDwGs variant, the |min| slot and the info kinds are the extended
+    // instance's alone, so the TD3 / SAC instance is byte for byte what the online programs ran on before)
+    if (offline3()) return KS_EXT;
     if (algo == RLE_TD7 && plan.wide && !(plan.fuse_on & RLE_FUSE_PRIOSAMPLE)) return KS_TD7W;  // (rb compiled in)
     if (plan.rb || (plan.fuse_on & RLE_FUSE_PRIOSAMPLE) || plan.wide) return KS_EXT;
     return algo == RLE_TD7 ? KS_TD7 : KS_MLP;
@@ -2865,6 +2889,12 @@ struct Engine {
     ad.bc2s = adam_bc2s_of(asc_set) + cnt;
     ad.lr = lr;
     ad.beta1 = 0.9f;
+    g.gscale = adam_gscale;
+    if (adam_gscale) {  // (the kDwGs variant: offline TD3's actor)
+      REQUIRE(!nb_x, "dw: no gradient scale with a deferred AvgL1Norm backward");
+      g.act = kDwGs;
+      rd.push_back(bc_s_id);
+    }
     ad.beta2 = 0.999f;
     ad.omb1 = (float)(1.0 - 0.9);
     ad.omb2 = (float)(1.0 - 0.999);
@@ -2900,6 +2930,9 @@ struct Engine {
   // (TD3 policy steps) tau of the self-aliased target-policy Polyak fused into the actor's Adam
   // epilogues (AdamArgs::ptau), 0 elsewhere
   float adam_ptau = 0.f;
+  // (offline TD3 policy steps) lmbda, which the actor's Adam epilogues multiply the gradient by
+  // (GemmArgs::gscale; OP_BC mode 3, or mode 2 behind the standalone head, writes it), nullptr elsewhere
+  const float* adam_gscale = nullptr;
   // (plan without RLE_FUSE_PIPOLYAK: the standalone OP_POLYAK over the policy instead, tests, A/B)
   bool pi_polyak_fused() const { return fused(RLE_FUSE_PIPOLYAK); }
 
@@ -3676,6 +3709,9 @@ struct Engine {
   // TD7 offline mode (rle_config bc_lambda > 0): OP_BC's outputs of the program being built -- q_abs, and the
   // row blocks' sums of (pi - a)^2
   bool offline() const { return algo == RLE_TD7 && cfg.bc_lambda > 0.f; }
+  // Offline TD3 (rle_config_ext bc_alpha > 0, TD3+BC): the same outputs, bc_s = {q_abs, lmbda}
+  float bc_alpha = 0.f;
+  bool offline3() const { return algo == RLE_TD3 && bc_alpha > 0.f; }
   float* bc_s = nullptr;
   float* bc_part = nullptr;
   int bc_s_id = -1, bc_part_id = -1, bc_part_n = 0;
@@ -4133,6 +4169,66 @@ struct Engine {
                        dsrc_of(actC, pc[n][D - 2], pcz[n][D - 2]));
         out_t = true;
       }
+      // ---- offline (rle_config_ext bc_alpha): L = -lmbda mean(min Q) + mse(pi(s), a), lmbda = bc_alpha /
+      // mean|min Q| (detached).  Scale at the end: the chain above and below stays the online one (dL/dq = -1/B),
+      // so it carries the gradient of L / lmbda; the cloning term enters the action gradient as e0 x (q_abs /
+      // bc_alpha) I (one more reduction segment ahead of tanh', TD7's construction), and the actor's Adam
+      // epilogues multiply by lmbda.  OP_BC mode 0 needs the actor output alone (many levels earlier); q_abs
+      // comes from the policy pass's row partials beside the fused head (mode 3) or from the standalone head's
+      // |min| partials a level after it (mode 2): either way it is ready a level before the action gradient.
+      View bc_e, bc_eye;
+      bc_s = nullptr;
+      if (offline3()) {
+        REQUIRE(A <= kThreads && a_pi.m.n && act_in.m.n, "bc: operand layout");
+        bc_e = buf(B, A, true, false);
+        bc_part_n = cdiv(Bv, 16);
+        bc_part = mem.make<float>((size_t)bc_part_n);
+        bc_part_id = next_id++;
+        {
+          Op op{};
+          op.kind = OP_BC;
+          BcArgs& b = op.bc;
+          b.mode = 0;
+          b.nvalid = Bv;
+          b.A = A;
+          b.lambda = 1.f;
+          b.pi = a_pi.m;
+          b.a = act_in.m;
+          b.e = bc_e.m;
+          b.part = bc_part;
+          op.wg_count = bc_part_n;
+          pg.add(op, {a_pi.id, act_in.id}, {bc_e.id, bc_part_id});
+        }
+        bc_eye = buf(A, A, false, true);
+        bc_s = mem.make<float>(4);
+        bc_s_id = next_id++;
+        Op op{};
+        op.kind = OP_BC;
+        BcArgs& b = op.bc;
+        b.lambda = bc_alpha;
+        b.nvalid = Bv;
+        b.A = A;
+        b.eye = bc_eye.m;
+        b.out = bc_s;
+        op.wg_count = 1;
+        if (hdx) {  // (the row partials the fused head reads: this op sits beside it, no level gained)
+          b.mode = 3;
+          for (int n = 0; n < 2; ++n) {
+            b.qp[n] = p1[n].qd;
+            b.qp_n[n] = p1[n].qd_n;
+            b.qb[n] = bias(*qo[n]);
+          }
+          REQUIRE(p1[0].qd && p1[1].qd && p1[0].qd_ld == p1[1].qd_ld, "bc: q partial layout");
+          b.qp_ld = p1[0].qd_ld;
+          pg.add(op, {p1[0].qd_id, p1[1].qd_id, qo[0]->res, qo[1]->res}, {bc_eye.id, bc_s_id});
+        } else {  // (the standalone head's |min| partials, a level after it and a level before the action gradient)
+          b.mode = 2;
+          b.qp[0] = ploss_part + 1;
+          b.qp_n[0] = hw;
+          b.qp_ld = 4;
+          pg.add(op, {ploss_id}, {bc_eye.id, bc_s_id});
+        }
+      }
       // (deeper critics: on down to the first hidden layer; no weight gradient reads these)
       out_t = false;
       for (int i = D - 2; i >= 1; --i)
@@ -4142,8 +4238,11 @@ struct Engine {
       View dout;
       PreUse pdout{};  // TD3: d1 recomputes dout in-tile
       if (!sac) {
-        dout = dx(pg, {{dzp0[0], &q[0]->layers[0], Sp}, {dzp0[1], &q[1]->layers[0], Sp}}, A, B, ACT_TANH, &a_pi);
-        if (prea) pdout = pre_actor_dx({{dzp0[0], &q[0]->layers[0], Sp}, {dzp0[1], &q[1]->layers[0], Sp}}, A, a_pi, 0);
+        std::vector<DxTerm> ta{{dzp0[0], &q[0]->layers[0], Sp}, {dzp0[1], &q[1]->layers[0], Sp}};
+        // (offline: the cloning gradient, in the in-tile recomputation as well, so RLE_FUSE_PRE stays)
+        if (offline3()) ta.push_back({bc_e, nullptr, 0, &bc_eye});
+        dout = dx(pg, ta, A, B, ACT_TANH, &a_pi);
+        if (prea) pdout = pre_actor_dx(ta, A, a_pi, 0);
       } else {
         dout = buf(B, 2 * A);
         if (sac_bwd_fused()) {  // the backward in the epilogue of the DX that forms da (one level fewer)
@@ -4215,6 +4314,7 @@ struct Engine {
       // TD3: the aliased target policy's Polyak (td3.py:200-204) in the Adam epilogues: one level
       // fewer between the actor update and the next step's target action
       adam_ptau = !sac && pi_polyak_fused() ? cfg.tau : 0.f;
+      adam_gscale = offline3() ? bc_s + 1 : nullptr;
       // SAC: d1 (the gradient through the raw head, K = 2A <= 48) recomputed in-tile by d0's DX
       const bool pld = sac && sac_bwd_fused() && prelayer_ok_dx(Lout, pi.layers[D - 1]);
       pl_src = pld;
@@ -4236,6 +4336,7 @@ struct Engine {
       }
       dw(pg, pi.layers[0], d, {s}, B, CNT_ADAM_PI, cfg.policy_lr, gl[0].first, gl[0].second);
       adam_ptau = 0.f;
+      adam_gscale = nullptr;
       if (gsq) {
         // tensor t owns tiles [gsq_offs[t], gsq_offs[t+1]) (params() order: w0, b0, w1, b1, ...)
         gsq_offs.assign(1, 0);
@@ -4272,6 +4373,19 @@ struct Engine {
         a.kind[2] = INFO_NAN;
       }
       a.ninfo = 3;
+      if (offline3()) {  // [train/q_fn, train/policy, norm/policy, train/bc, train/lmbda]
+        a.ninfo = 5;
+        if (policy) {
+          a.kind[1] = INFO_SUM_BC3;  // lmbda * -mean(min Q) + bc
+          a.bcs = bc_s;
+          info_sum(a, 3, bc_part, bc_part_n, 1, 1.f / ((float)Bv * (float)A));
+          a.kind[4] = INFO_BCS1;
+          rd.push_back(bc_s_id);
+          rd.push_back(bc_part_id);
+        } else {
+          a.kind[3] = a.kind[4] = INFO_NAN;
+        }
+      }
     } else if (cfg.tmp < 0.f) {  // [train/q_fn, tmp, norm/tmp, train/policy, train/tmp, entropy]
       info_sum(a, 0, qloss_part, hw * 4, 1, 0.5f / (float)Bv);
       a.kind[1] = INFO_SAC_TMP;
@@ -4366,6 +4480,7 @@ struct Engine {
           static const char* kepi[] = {"st", "adam", "mse", "qhead", "nbdot", "act", "qdot", "sacbwd", "sacfwd"};
           static_assert(sizeof(kepi) / sizeof(kepi[0]) == EPI_SACFWD + 1, "every epilogue has a name");
           const char* ep = op.gemm.mode == GEMM_DW && op.gemm.act == kDwNb ? "adam+nb"
+                           : op.gemm.mode == GEMM_DW && op.gemm.act == kDwGs ? "adam+gs"
                            : op.gemm.has_pre == 2                         ? "head+dx"
                            : op.gemm.has_pre == 3                         ? (op.gemm.epi == EPI_QDOT ? "qdot+pl" : "st+pl")
                            : op.gemm.has_pre == 4                         ? "qdot+pl2"
@@ -5340,6 +5455,80 @@ int rle_replay_set_state(rle_replay* h, long long ptr, long long size, float max
   });
 }
 
+// The stats launch shape of a replay's `state` over rows [0, size) (ops.h ReplayStatArgs)
+static rle::ReplayStatArgs stat_args(Replay& r, const float* x) {
+  rle::ReplayStatArgs a{};
+  a.x = x;
+  a.size = r.size;
+  a.Sp = r.Sp;
+  a.rows_wg = rle::stat_rows_wg(r.size, r.Sp);
+  a.nwg = rle::stat_nwg(r.size, r.Sp);
+  return a;
+}
+
+int rle_replay_state_stats(rle_replay* h, float* mean, float* std_out) {
+  return guard([&] {
+    REQUIRE(h && mean && std_out, "state_stats: null argument");
+    Replay& r = h->r;
+    if (r.size <= 0) throw Error{RLE_ESTATE, "state_stats: empty replay"};
+    HIPCHK(hipSetDevice(r.device));
+    r.wait_users();
+    rle::ReplayStatArgs a = stat_args(r, r.state);
+    a.part = r.scratch.get<double>("stat_part", (size_t)a.nwg * r.Sp);
+    double* md = r.scratch.get<double>("stat_mean_d", r.Sp);
+    double* sd = r.scratch.get<double>("stat_std_d", r.Sp);
+    float* mf = r.scratch.get<float>("stat_mean_f", r.Sp);
+    float* sf = r.scratch.get<float>("stat_std_f", r.Sp);
+    // pass 1: the means; pass 2: the centred squares (each: per-workgroup partials, then their sum in order)
+    HIPCHK(rle::launch_replay_colsum(a, r.stream));
+    a.out_d = md;
+    a.out_f = mf;
+    HIPCHK(rle::launch_replay_colfin(a, r.stream));
+    a.center = md;
+    HIPCHK(rle::launch_replay_colsum(a, r.stream));
+    a.out_d = sd;
+    a.out_f = sf;
+    a.sq = 1;
+    HIPCHK(rle::launch_replay_colfin(a, r.stream));
+    HIPCHK(hipMemcpyAsync(mean, mf, (size_t)r.S * 4, hipMemcpyDeviceToHost, r.stream));
+    HIPCHK(hipMemcpyAsync(std_out, sf, (size_t)r.S * 4, hipMemcpyDeviceToHost, r.stream));
+    HIPCHK(hipStreamSynchronize(r.stream));
+  });
+}
+
+int rle_replay_normalize_states(rle_replay* h, const float* shift, const float* scale) {
+  return guard([&] {
+    REQUIRE(h && shift && scale, "normalize_states: null argument");
+    Replay& r = h->r;
+    for (int j = 0; j < r.S; ++j) {
+      REQUIRE(std::isfinite(shift[j]), "normalize_states: shift must be finite");
+      REQUIRE(std::isfinite(scale[j]) && scale[j] != 0.f, "normalize_states: scale must be finite and non-zero");
+    }
+    if (r.size <= 0) throw Error{RLE_ESTATE, "normalize_states: empty replay"};
+    HIPCHK(hipSetDevice(r.device));
+    r.wait_users();
+    // padded to Sp: a pad column computes (0 - 0) / 1, so it keeps the zero every first-layer GEMM relies on
+    std::vector<float> hp(2 * (size_t)r.Sp, 0.f);
+    for (int j = 0; j < r.Sp; ++j) hp[r.Sp + j] = 1.f;
+    std::memcpy(hp.data(), shift, (size_t)r.S * 4);
+    std::memcpy(hp.data() + r.Sp, scale, (size_t)r.S * 4);
+    float* dp = r.scratch.get<float>("norm_vec", 2 * (size_t)r.Sp);
+    HIPCHK(hipMemcpyAsync(dp, hp.data(), hp.size() * 4, hipMemcpyHostToDevice, r.stream));
+    rle::ReplayNormArgs a{};
+    a.x[0] = r.state;
+    a.x[1] = r.next_state;
+    a.size = r.size;
+    a.Sp = r.Sp;
+    a.rows_wg = rle::stat_rows_wg(r.size, r.Sp);
+    a.nwg = rle::stat_nwg(r.size, r.Sp);
+    a.shift = dp;
+    a.scale = dp + r.Sp;
+    HIPCHK(rle::launch_replay_normalize(a, r.stream));
+    HIPCHK(hipStreamSynchronize(r.stream));
+    ++r.version;  // (bound engines redraw their prefetched batch, as after rle_replay_set_state)
+  });
+}
+
 int rle_replay_copy(rle_replay* hd, rle_replay* hs) {
   return guard([&] {
     REQUIRE(hd && hs, "copy: null replay");
@@ -5375,9 +5564,18 @@ int rle_replay_copy(rle_replay* hd, rle_replay* hs) {
   });
 }
 
-int rle_create(const rle_config* cfg, rle_engine** out) {
+int rle_create(const rle_config* cfg, rle_engine** out) { return rle_create_ext(cfg, nullptr, out); }
+
+int rle_create_ext(const rle_config* cfg, const rle_config_ext* ext, rle_engine** out) {
   return guard([&] {
     REQUIRE(cfg && out, "create: null");
+    // the extension as the caller compiled it: fields past ext->size read as 0
+    rle_config_ext x{};
+    if (ext) {
+      REQUIRE(ext->size >= (int)(offsetof(rle_config_ext, bc_alpha) + sizeof(float)),
+              "create: rle_config_ext size does not reach bc_alpha");
+      std::memcpy(&x, ext, std::min<size_t>((size_t)ext->size, sizeof x));
+    }
     REQUIRE(cfg->algo >= 0 && cfg->algo <= 2, "create: bad algo");
     REQUIRE(cfg->batch > 0 && cfg->batch <= 1024, "create: batch must be in 1..1024");
     REQUIRE(cfg->state_dim <= 1024 && cfg->action_dim <= 128 && cfg->hidden <= 512,
@@ -5396,11 +5594,14 @@ int rle_create(const rle_config* cfg, rle_engine** out) {
     REQUIRE(cfg->algo == RLE_TD7 || cfg->act_encoder == RLE_ACT_DEFAULT, "create: act_encoder is TD7's (SALEEncoder)");
     REQUIRE(cfg->bc_lambda >= 0.f && std::isfinite(cfg->bc_lambda), "create: bc_lambda must be a finite value >= 0");
     REQUIRE(cfg->bc_lambda == 0.f || cfg->algo == RLE_TD7, "create: bc_lambda (offline mode) is TD7's");
+    REQUIRE(x.bc_alpha >= 0.f && std::isfinite(x.bc_alpha), "create: bc_alpha must be a finite value >= 0");
+    REQUIRE(x.bc_alpha == 0.f || cfg->algo == RLE_TD3, "create: bc_alpha (offline mode, TD3+BC) is TD3's");
     HIPCHK(hipSetDevice(cfg->device));
     auto h = std::make_unique<rle_engine>();
     h->e = std::make_unique<Engine>();
     Engine& e = *h->e;
     e.cfg = *cfg;
+    e.bc_alpha = x.bc_alpha;
     e.algo = cfg->algo;
     e.S = cfg->state_dim;
     e.Sp = rle::r16(e.S);

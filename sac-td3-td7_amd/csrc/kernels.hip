@@ -2124,11 +2124,16 @@ __device__ __forceinline__ void gemm_v(const CAS GemmArgs& g, int t, float* smem
     float gg = 0.f;
     if (jok) {
       const float step_size = sload(ad.step), bc2s = sload(ad.bc2s);  // this step's (level-0 CTRL op)
+      // (kDwGs, offline TD3: the chain carried the gradient of L / lmbda, and this variant's epilogue multiplies
+      // by lmbda, GemmArgs::gscale; every other weight gradient takes the gradient as it is)
+      constexpr bool GSC = MODE == GEMM_DW && ACT == kDwGs;
+      float gs = 1.f;
+      if constexpr (GSC) gs = sload(g.gscale);
       const float p4[4] = {pp.x, pp.y, pp.z, pp.w}, m4[4] = {mm.x, mm.y, mm.z, mm.w}, v4[4] = {vv.x, vv.y, vv.z, vv.w};
       float po[4], mo[4], vo[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const float gv = acc[q];
+        const float gv = GSC ? acc[q] * gs : acc[q];
         const float m = m4[q] + ad.omb1 * (gv - m4[q]);
         const float v2 = v4[q] * ad.beta2 + (ad.omb2 * gv) * gv;
         const float denom = sqrtf(v2) / bc2s + ad.eps;
@@ -2238,7 +2243,7 @@ __device__ __forceinline__ void op_normbwd(const CAS NormBwdArgs& a, int t) {
 // row per wave (4 per workgroup): lane l holds columns 4l..4l+3 (+256 per pass)
 // as float4s of the N images, so every operand of the row -- both twins' hidden
 // layer, weights and derivative source -- is loaded in one round trip.
-template <int DACT>
+template <int DACT, bool BC3>  // (BC3: offline TD3's |min| slot -- the extended instance alone, which runs its programs)
 __device__ __forceinline__ void op_head_t(const CAS HeadArgs& h, int t, float* smem, unsigned long long* tr) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int b = t * 4 + wave;  // wave-uniform: per-row scalars come through s_load
@@ -2360,6 +2365,8 @@ __device__ __forceinline__ void op_head_t(const CAS HeadArgs& h, int t, float* s
           acc1 = lp;
         } else {
           acc0 = mn;
+          // (slot 1 of the partials: sum |min|, read by the offline TD3 step's OP_BC mode 2 alone)
+          if constexpr (BC3) acc1 = fabsf(mn);
         }
       }
     }
@@ -2409,10 +2416,11 @@ __device__ __forceinline__ void op_head_t(const CAS HeadArgs& h, int t, float* s
   }
 }
 
+template <bool BC3>
 __device__ __forceinline__ void op_head(const CAS HeadArgs& h, int t, float* smem, unsigned long long* tr) {
-  if (h.dact == ACT_ELU) op_head_t<ACT_ELU>(h, t, smem, tr);
-  else if (h.dact == ACT_RELU) op_head_t<ACT_RELU>(h, t, smem, tr);
-  else op_head_t<ACT_NONE>(h, t, smem, tr);
+  if (h.dact == ACT_ELU) op_head_t<ACT_ELU, BC3>(h, t, smem, tr);
+  else if (h.dact == ACT_RELU) op_head_t<ACT_RELU, BC3>(h, t, smem, tr);
+  else op_head_t<ACT_NONE, BC3>(h, t, smem, tr);
 }
 
 // ---------------------------------------------------------------- replay sampling
@@ -2923,7 +2931,7 @@ __device__ __forceinline__ void adam_scalars(long long t, float lr, GAS float* s
 // elements of every sum (independent loads, one memory round trip), parks its
 // per-sum partials in LDS, then wave w reduces sums w, w+4, ... (fixed order).
 // (SAC: the temperature terms, compiled into the TD3 / SAC and extended instances only)
-template <bool SAC>
+template <bool SAC, bool BC3>  // (BC3: offline TD3's info kinds -- the extended instance alone)
 __device__ __forceinline__ void op_step_end(const CAS StepEndArgs& a, float* smem, unsigned long long* tr) {
   constexpr int kSums = kInfoMax + 1 + kGsqT;  // info sums, logpi, grad-norm tensors
   float* res = smem + kSums * kThreads;    // [kSums]
@@ -2947,6 +2955,7 @@ __device__ __forceinline__ void op_step_end(const CAS StepEndArgs& a, float* sme
   // (TD7 offline: OP_BC's q_abs and bc for the policy objective's second term)
   const bool bcv = w0 && a.bcs && mode != 1;
   const float bc_q = bcv ? G(a.bcs)[0] : 0.f;
+  const float bc_l = BC3 && bcv && a.kind[1] == INFO_SUM_BC3 ? G(a.bcs)[1] : 0.f;  // (offline TD3: lmbda)
   FINE_MARK(0);
   // sum list: j < ninfo -> info k (if summed); kInfoMax -> logpi; kInfoMax+1+q -> gsq tensor q
   auto sum_src = [&](int j, const float*& p, int& n, int& stride) {
@@ -2954,7 +2963,8 @@ __device__ __forceinline__ void op_step_end(const CAS StepEndArgs& a, float* sme
     n = 0;
     stride = 1;
     if (j < kInfoMax) {
-      if (j < a.ninfo && (a.kind[j] == INFO_SUM || a.kind[j] == INFO_SAC_POL || a.kind[j] == INFO_SUM_BC)) {
+      if (j < a.ninfo && (a.kind[j] == INFO_SUM || a.kind[j] == INFO_SAC_POL || a.kind[j] == INFO_SUM_BC ||
+                          (BC3 && a.kind[j] == INFO_SUM_BC3))) {
         p = a.part[j];
         n = a.npart[j];
         stride = a.stride[j];
@@ -3043,6 +3053,8 @@ __device__ __forceinline__ void op_step_end(const CAS StepEndArgs& a, float* sme
       case INFO_SAC_TMPL: v = tmp_obj; break;
       case INFO_SAC_ENT: v = -slp * a.inv_b; break;
       case INFO_SUM_BC: v = v * a.scale[k] + (a.bc_lambda * bc_q) * (vals[k + 1] * a.scale[k + 1]); break;
+      case INFO_SUM_BC3: if constexpr (BC3) v = bc_l * (v * a.scale[k]) + vals[k + 2] * a.scale[k + 2]; break;
+      case INFO_BCS1: if constexpr (BC3) v = bc_l; break;
     }
     if (tid == k) mine = v;
   }
@@ -3132,6 +3144,7 @@ __device__ __forceinline__ void op_foldbias(const CAS FoldBiasArgs& f) {
 // ---------------------------------------------------------------- behaviour-cloning term (TD7 offline)
 // (ops.h BcArgs; off the step's chain.  Small loops on purpose: a one-workgroup op's cold code is fetched at L2
 // latency, and an unrolled version of this op was the longest of its level)
+template <bool BC3>  // (BC3: modes 2 and 3, offline TD3 -- the extended instance alone)
 __device__ __forceinline__ void op_bc(const CAS BcArgs& b, int t, float* smem) {
   const int tid = threadIdx.x;
   const int B = b.nvalid, A = b.A;
@@ -3150,12 +3163,32 @@ __device__ __forceinline__ void op_bc(const CAS BcArgs& b, int t, float* smem) {
     if (tid == 0) GW(b.part)[t] = d2;
     return;
   }
+  if (BC3 && b.mode == 2) {  // offline TD3: q_abs from the policy head's |min| partials, lmbda, (q_abs / alpha) I
+    float sa = 0.f;
+    for (int i = tid; i < b.qp_n[0]; i += kThreads) sa += G(b.qp[0])[(size_t)i * b.qp_ld];
+    const float q_abs = wg_sum(sa, smem) / (float)B;
+    if (tid == 0) {
+      GW(b.out)[0] = q_abs;
+      GW(b.out)[1] = b.lambda / q_abs;
+    }
+    if (tid < A) GW(b.eye.t)[tidx(b.eye.rbs, tid, tid)] = q_abs / b.lambda;
+    return;
+  }
   const float b0 = G(b.qb[0])[0], b1 = G(b.qb[1])[0];
   float qa = 0.f;
   for (int r = tid; r < B; r += kThreads) {  // (a row's partials in column-tile order, 16 loads at a time)
     const float q0 = norm_mean_i(b.qp[0], b.qp_ld, r, b.qp_n[0], 1);
     const float q1 = norm_mean_i(b.qp[1], b.qp_ld, r, b.qp_n[1], 1);
-    qa += fabsf(q0 + b0) + fabsf(q1 + b1);
+    qa += BC3 && b.mode == 3 ? fabsf(fminf(q0 + b0, q1 + b1)) : fabsf(q0 + b0) + fabsf(q1 + b1);
+  }
+  if (BC3 && b.mode == 3) {  // offline TD3 with the fused head: as mode 2, from the row partials, beside the head
+    const float q_abs = wg_sum(qa, smem) / (float)B;
+    if (tid == 0) {
+      GW(b.out)[0] = q_abs;
+      GW(b.out)[1] = b.lambda / q_abs;
+    }
+    if (tid < A) GW(b.eye.t)[tidx(b.eye.rbs, tid, tid)] = q_abs / b.lambda;
+    return;
   }
   const float q_abs = wg_sum(qa, smem) / (2.f * (float)B);
   if (tid == 0) GW(b.out)[0] = q_abs;
@@ -3252,11 +3285,11 @@ __global__ __launch_bounds__(kThreads, RLE_WAVES) void rle_level(unsigned e0, un
     RLE_OP(OP_NORMBWD, op_normbwd(op.nb, t))
     RLE_OP(OP_SAMPLE_REDUCE, op_sample_reduce(op.sample, t, smem))
     RLE_OP(OP_SAMPLE_GATHER, op_sample_gather<KS == KS_EXT>(op.sample, t, smem, tr))
-    RLE_OP(OP_HEAD, op_head(op.head, t, smem, tr))
+    RLE_OP(OP_HEAD, op_head<KS == KS_EXT>(op.head, t, smem, tr))
     RLE_OP(OP_PRIORITY, op_priority(op.prio, smem))
     RLE_OP(OP_SAC_ACTOR, op_sac_actor(op.sac, t))
     RLE_OP(OP_SAC_ACTOR_BWD, op_sac_actor_bwd(op.sac, t))
-    RLE_OP(OP_STEP_END, op_step_end<ks_family(KS) != KS_TD7>(op.end, smem, tr))
+    RLE_OP(OP_STEP_END, (op_step_end<ks_family(KS) != KS_TD7, KS == KS_EXT>(op.end, smem, tr)))
     RLE_OP(OP_POLYAK, op_polyak(op.flat, t))
     RLE_OP(OP_COPY, op_copy(op.flat, t))
     RLE_OP(OP_MAXRED, op_maxred(op.flat, t, smem))
@@ -3264,7 +3297,7 @@ __global__ __launch_bounds__(kThreads, RLE_WAVES) void rle_level(unsigned e0, un
     RLE_OP(OP_NOISE, op_noise(op.sample, t))
     RLE_OP(OP_FOLDBIAS, op_foldbias(op.fb))
     // (kinds past 15, ops.h OpKind: low bits 0, kind >> 4 in the variant field; the TD7 family's instances)
-    RLE_OP(0, if (ks_family(KS) != KS_MLP && vid == (OP_BC >> 4)) op_bc(op.bc, t, smem))
+    RLE_OP(0, if (ks_family(KS) != KS_MLP && vid == (OP_BC >> 4)) op_bc<KS == KS_EXT>(op.bc, t, smem))
 #undef RLE_OP
     default: break;
   }

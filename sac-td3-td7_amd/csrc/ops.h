@@ -122,6 +122,10 @@ struct ActArgs {
 // GEMM_DW variant whose A operand (dZ) is an AvgL1Norm backward applied on load:
 // a = g / m + sign(x) * gm, gm = -(sum_j g x) / (n m^2) (0 when m is clamped), rows by LDS table
 constexpr int kDwNb = 1;  // (in the act slot of a DW variant id)
+// GEMM_DW variant whose Adam epilogue multiplies the accumulated gradient by the device scalar GemmArgs::gscale
+// (offline TD3's lmbda) before the moments and the gsq partials.  The extended instance alone holds
+// it: offline TD3 programs run there, so the TD3 / SAC instance is the code it was for the online programs.
+constexpr int kDwGs = 2;  // (in the act slot of a DW variant id)
 
 struct AdamArgs {
   Mat w;                 // weight images [N out rows][K cols] (both kept: FWD reads N, DX reads T)
@@ -140,7 +144,7 @@ struct AdamArgs {
 
 // Variant id of a GEMM op = pre * 512 + mode * 128 + epi * 8 + act * 2 + norm (pre: one A
 // segment is the actor's tanh output layer recomputed in the workgroup, PreArgs; act: the forward
-// activation for GEMM_FWD, the derivative mask for GEMM_DX, kDwNb or 0 for GEMM_DW; norm: some operand
+// activation for GEMM_FWD, the derivative mask for GEMM_DX, kDwNb, kDwGs or 0 for GEMM_DW; norm: some operand
 // segment carries a deferred AvgL1Norm).
 constexpr int gemm_vid(int mode, int epi, int act, int norm, int pre = 0) {
   return pre * 512 + mode * 128 + epi * 8 + act * 2 + norm;
@@ -181,6 +185,7 @@ static_assert(gemm_vid(2, 8, 15, 1, 3) < 2048, "GEMM variant ids fit 11 bits");
   X(GEMM_DW, EPI_ADAM, ACT_NONE, 0, 0, 0, 3)        \
   X(GEMM_DW, EPI_ADAM, ACT_NONE, 1, 0, 0, 1)        \
   X(GEMM_DW, EPI_ADAM, kDwNb, 0, 0, 0, 1)           \
+  X(GEMM_DW, EPI_ADAM, kDwGs, 0, 0, 0, 0)           \
   X(GEMM_FWD, EPI_STORE, ACT_NONE, 0, 1, 1, 1)      \
   X(GEMM_FWD, EPI_STORE, ACT_RELU, 0, 1, 1, 3)      \
   X(GEMM_FWD, EPI_STORE, ACT_ELU, 1, 1, 1, 1)       \
@@ -402,7 +407,10 @@ struct GemmArgs {
   // prea2.seg is itself computed in-tile first, by the pre-GEMM prea2 (the target action), so the
   // first layer behind the target action costs no level of its own
   PreArgs prea2;
-  int pad_tail_[2];                // (Op: whole 64-byte lines)
+  // kDwGs variants [1]: the accumulated gradient times this device scalar before the moments and gsq (offline TD3:
+  // lmbda of the scale-at-the-end design, BcArgs modes 2 / 3); null in every other op.  (In the place of the tail
+  // padding: Op stays whole 64-byte lines and every other field where it was.)
+  const float* gscale;
 };
 
 // AvgL1Norm backward: dx = (g - sign(x) * (sum g*y)/n) / m, y = x/m (row-wise);
@@ -496,6 +504,7 @@ struct StepEndArgs {
   int mode;
   float* sac_scratch;
   // TD7 offline (INFO_SUM_BC): OP_BC's q_abs [1] and lmbda (bc is the next info column's own sum)
+  // offline TD3 (INFO_SUM_BC3 / INFO_BCS1): {q_abs, lmbda} of OP_BC mode 3 (mode 2 behind the standalone head)
   const float* bcs; float bc_lambda;
 };
 
@@ -509,6 +518,8 @@ enum InfoKind : int {
   INFO_SAC_TMPL = 6,  // tmp_obj
   INFO_SAC_ENT = 7,   // -mean(logpi)
   INFO_SUM_BC = 8,    // scale * sum + bc_lambda * bcs[0] * (info k + 1: scale * sum) (TD7 offline train/policy)
+  INFO_SUM_BC3 = 9,   // bcs[1] * (scale * sum) + (info k + 2: scale * sum) (offline TD3 train/policy: lmbda * -mean(Q) + bc)
+  INFO_BCS1 = 10,     // bcs[1] (offline TD3 train/lmbda)
 };
 
 // Bias of a layer whose input block [col0, col0 + H) is fed by a linear layer folded
@@ -536,6 +547,21 @@ struct FoldBiasArgs {
 // of tanh'.  Summation order: mode 0 thread t of block rb adds its elements t, t + 256, ... of the block's
 // [16][A] (row-major), mode 1 thread t the rows t, t + 256, ... (a row's partials in column-tile order); then
 // wg_sum.  Fixed by B, A and the partials' tile width alone, whatever the launch order.
+//
+// Offline TD3 (rle_config_ext bc_alpha > 0), L = -lmbda mean(min Q) + mse(pi, a), lmbda = bc_alpha / mean|min Q|
+// (detached): the backward chain stays the online one (dL/dq = -1/B), i.e. it differentiates L / lmbda, and the
+// actor's Adam epilogues multiply the accumulated gradient by lmbda (GemmArgs::gscale).  Mode 0 runs with
+// lambda = 1 (e0 = 2 (pi - a) / (nvalid A)); the standalone policy head (OP_HEAD) leaves sum |min(q1, q2)| of its
+// 4-row groups in slot 1 of its loss partials, and
+//   mode 2 (a level after the head; one workgroup): qp[0] = those partials, qp_n[0] of them, qp_ld floats apart,
+//       lambda = bc_alpha:
+//       out[0] = q_abs = sum / nvalid,  out[1] = lmbda = bc_alpha / q_abs (no guard for q_abs = 0, as the
+//       paper's code),  eye = (q_abs / bc_alpha) I
+//     so e0 x eye = dL_bc / d pi / lmbda.  Summation order: thread t adds partials t, t + 256, ...; then wg_sum.
+//   mode 3 (the head fused into the DX of the last hidden layer, RLE_FUSE_HEADDX: the policy pass's EPI_QDOT row
+//     partials exist a level before the head, so this op runs BESIDE the head and the step gains no level; one
+//     workgroup): mode 2's outputs with q_abs = sum_i |min(q1_i, q2_i)| / nvalid from the partials qp / qb, as
+//     mode 1 reads them (thread t the rows t, t + 256, ..., a row's partials in column-tile order; then wg_sum).
 struct BcArgs {
   int mode;
   int nvalid, A;
@@ -695,6 +721,43 @@ struct ReplayPackArgs {
 };
 // rows per workgroup tile of a field of padded width wp (host and device agree on the tile split)
 constexpr int pack_tile_rows(int wp) { return kPackTile / wp < kPackTileRows ? kPackTile / wp : kPackTileRows; }
+
+// ---- dataset state normalisation (replay_norm.hip rle_replay_colsum / rle_replay_colfin / rle_replay_normalize;
+// rle_replay_state_stats, rle_replay_normalize_states).  Ring rows of Sp floats move as 16-byte vectors: a
+// workgroup's threads 0 .. rpi * Sp/4 - 1 read rpi = max(1, 256 / (Sp/4)) consecutive rows per iteration, one
+// contiguous run of bytes; thread t keeps column vector t % (Sp/4) of rows r0 + t / (Sp/4), + rpi, ...
+// Statistics, fp64 throughout: workgroup w of nwg sums its rows [w rows_wg, (w + 1) rows_wg) -- each thread its
+// rows in ascending order, then the rpi row lanes in ascending order -- into part[w][Sp]; rle_replay_colfin
+// adds the nwg partials in ascending w.  stat_nwg fixes nwg from size and S alone, so the summation order
+// does not depend on the device or the launch.
+constexpr int kStatMaxWg = 1024;
+constexpr int stat_rpi(int Sp) { return kThreads / (Sp / 4) > 0 ? kThreads / (Sp / 4) : 1; }
+constexpr long long stat_rows_wg(long long size, int Sp) {  // rows per workgroup: a multiple of rpi, >= 64 iterations
+  long long per = (long long)stat_rpi(Sp) * 64;
+  long long need = (size + kStatMaxWg - 1) / kStatMaxWg;
+  need = (need + stat_rpi(Sp) - 1) / stat_rpi(Sp) * stat_rpi(Sp);
+  return need > per ? need : per;
+}
+constexpr int stat_nwg(long long size, int Sp) {
+  return (int)((size + stat_rows_wg(size, Sp) - 1) / stat_rows_wg(size, Sp));
+}
+struct ReplayStatArgs {
+  const float* x;        // ring field [cap][Sp]
+  long long size;        // rows [0, size)
+  long long rows_wg;     // stat_rows_wg
+  int Sp, nwg;
+  const double* center;  // null: sum x; else sum (x - center[j])^2   [Sp]
+  double* part;          // [nwg][Sp]
+  // rle_replay_colfin: out_d[j] = sum_w part[w][j] / size (sq: its sqrt); out_f the same rounded to fp32
+  double* out_d; float* out_f; int sq;
+};
+struct ReplayNormArgs {
+  float* x[2];           // state, next_state rings [cap][Sp]
+  long long size, rows_wg;
+  int Sp, nwg;           // nwg workgroups per field
+  const float* shift;    // [Sp] (pad columns: 0)
+  const float* scale;    // [Sp] (pad columns: 1, so a pad column keeps its zero: (0 - 0) / 1)
+};
 
 // ---- agent state pack / unpack (kernels.hip rle_state_pack / rle_state_unpack): the selected tensors of the
 // params | m | v arenas <-> one packed image of logical row-major tensors (state_dict() layout: weights

@@ -48,6 +48,18 @@ class Config(ctypes.Structure):
     ]
 
 
+class ConfigExt(ctypes.Structure):
+    """Mirror of ``rle_config_ext`` (include/rle.h): settings added after ``rle_config`` was frozen.
+    ``size`` is what this mirror knows of the struct; the library reads every field past it as 0."""
+
+    _fields_ = [("size", _int), ("bc_alpha", ctypes.c_float)]
+
+
+def make_config_ext(bc_alpha=0.0) -> ConfigExt:
+    """``bc_alpha`` (TD3): 0 online; > 0 the offline (TD3+BC) policy step's alpha (rle_config_ext bc_alpha)."""
+    return ConfigExt(ctypes.sizeof(ConfigExt), float(bc_alpha))
+
+
 # rle_config act_* codes (include/rle.h RLE_ACT_*): 0 = the reference default of that net
 ACT_CODES = {"default": 0, "relu": 1, "elu": 2, "identity": 3}
 
@@ -155,7 +167,10 @@ SIGNATURES = {
     "rle_replay_import": (_int, [_vp, _ll, _ll, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]),
     "rle_replay_set_state": (_int, [_vp, _ll, _ll, ctypes.c_float]),
     "rle_replay_copy": (_int, [_vp, _vp]),
+    "rle_replay_state_stats": (_int, [_vp, _f32p, _f32p]),
+    "rle_replay_normalize_states": (_int, [_vp, _f32p, _f32p]),
     "rle_create": (_int, [ctypes.POINTER(Config), ctypes.POINTER(_vp)]),
+    "rle_create_ext": (_int, [ctypes.POINTER(Config), ctypes.POINTER(ConfigExt), ctypes.POINTER(_vp)]),
     "rle_destroy": (_int, [_vp]),
     "rle_plan_default": (_int, [ctypes.POINTER(Plan)]),
     "rle_set_plan": (_int, [_vp, ctypes.POINTER(Plan)]),
@@ -332,6 +347,19 @@ class Replay:
     def set_state(self, ptr, size, max_priority):
         _check(lib().rle_replay_set_state(self.h, int(ptr), int(size), float(max_priority)))
 
+    def state_stats(self):
+        """Per-feature (mean, population std) of ``state`` over the filled rows (rle_replay_state_stats: fp64
+        accumulation on the device, results in fp32)."""
+        m, s = np.empty(self.S, np.float32), np.empty(self.S, np.float32)
+        _check(lib().rle_replay_state_stats(self.h, _fp(m), _fp(s)))
+        return m, s
+
+    def normalize_states(self, shift, scale):
+        """state, next_state of the filled rows <- (x - shift) / scale on the device
+        (rle_replay_normalize_states)."""
+        shift, scale = _f32(shift, (self.S,)), _f32(scale, (self.S,))
+        _check(lib().rle_replay_normalize_states(self.h, _fp(shift), _fp(scale)))
+
     def copy_from(self, other: "Replay"):
         """This ring := other (rle_replay_copy: device to device, also across two GPUs)."""
         _check(lib().rle_replay_copy(self.h, other.h))
@@ -340,10 +368,14 @@ class Replay:
 class Engine:
     """One agent's device state + captured step graphs."""
 
-    def __init__(self, cfg: Config, plan: Plan | None = None):
+    def __init__(self, cfg: Config, plan: Plan | None = None, ext: ConfigExt | None = None):
         self.cfg = cfg
+        self.ext = ext
         self.h = _vp()
-        _check(lib().rle_create(ctypes.byref(cfg), ctypes.byref(self.h)))
+        if ext is None:
+            _check(lib().rle_create(ctypes.byref(cfg), ctypes.byref(self.h)))
+        else:
+            _check(lib().rle_create_ext(ctypes.byref(cfg), ctypes.byref(ext), ctypes.byref(self.h)))
         self.replay = None
         self._act_out = {}
         if plan is not None:

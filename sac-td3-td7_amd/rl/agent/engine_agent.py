@@ -31,6 +31,9 @@ class EngineAgent(Agent, Sampler):
     ALGO = -1         # RLE_TD7 / RLE_TD3 / RLE_SAC
     OPTIM_NETS: tuple = ()
     NULLABLE: tuple = ()  # info keys the reference sets to None on non-policy steps
+    # (class defaults: agents pickled before these existed load without them)
+    _ext: dict = {}   # rle_config_ext settings (make_config_ext), re-applied by every _new_engine
+    obs_norm = None   # (mean, scale) fed to the act path by sample(), set_obs_norm
 
     def _setup(self, env_id, *, hidden, batch_size, seed, device, make_nn, make_nn_kwargs, cfg):
         custom = None
@@ -93,7 +96,21 @@ class EngineAgent(Agent, Sampler):
     def _new_engine(self, batch):
         c = E.make_config(self.ALGO, self.state_dim, self.action_dim, self.hidden, batch, seed=self.seed,
                           device=self._device, **self._cfg, **self.shape, **getattr(self, "acts", {}))
-        return E.Engine(c)
+        ext = getattr(self, "_ext", None)
+        return E.Engine(c, ext=E.make_config_ext(**ext) if ext else None)
+
+    def set_obs_norm(self, mean, scale=None):
+        """``sample()`` feeds ``(obs - mean) / scale`` to the act path (fp32, on the host): the observation
+        side of a replay's ``normalize_states()``, whose return value this takes.  ``None`` clears it.
+        Pickled with the agent; nothing on the device act path changes."""
+        if mean is None:
+            self.obs_norm = None
+            return
+        m = np.ascontiguousarray(mean, np.float32).reshape(self.state_dim)
+        s = np.ascontiguousarray(scale, np.float32).reshape(self.state_dim)
+        if not (np.isfinite(m).all() and np.isfinite(s).all() and (s != 0).all()):
+            raise ValueError("set_obs_norm: mean must be finite, scale finite and non-zero")
+        self.obs_norm = (m.copy(), s.copy())
 
     @property
     def batch_size(self) -> int:
@@ -353,6 +370,8 @@ class EngineAgent(Agent, Sampler):
             eng._act_map = amap
         if hasattr(state, "detach"):
             state = state.detach().cpu().numpy()
+        if self.obs_norm is not None:
+            state = (np.asarray(state, np.float32) - self.obs_norm[0]) / self.obs_norm[1]
         if eps is not None:
             return eng.act_sample(state, 2, eps)[0].copy()
         return eng.act_sample(state, 0 if deterministic else 1)[0].copy()

@@ -12,18 +12,31 @@ class TD3(EngineAgent):
     """MLP actor + twin critics with target policy smoothing and delayed Polyak updates.
 
     Constructor arguments as the reference (td3.py:33-47) plus ``hidden``,
-    ``batch_size``, ``seed`` and ``device`` (see TD7)."""
+    ``batch_size``, ``seed`` and ``device`` (see TD7).
+
+    ``offline=True`` trains from a fixed dataset with TD3+BC (Fujimoto & Gu 2021): on policy steps the actor
+    objective is ``-lmbda * mean(Q) + mse(pi(s), a)`` with ``lmbda = alpha / mean|Q|.detach()`` (``a``: the
+    batch's stored action; ``Q = min(q1, q2)`` as this code base's TD3 objective), and the info dict gains two
+    keys, ``train/bc`` (the mse) and ``train/lmbda`` (None on other steps).  The recipe's state normalisation is
+    the replay's ``normalize_states()`` and the agent's ``set_obs_norm``.  ``offline=False`` ignores ``alpha``.
+    """
 
     ALG = "td3"
     ALGO = E.RLE_TD3
     OPTIM_NETS = ("policy", "q1", "q2")
-    NULLABLE = ("train/policy", "norm/policy")
+    NULLABLE = ("train/policy", "norm/policy", "train/bc", "train/lmbda")
+    offline = False  # (class defaults: an agent pickled before the offline mode existed loads as online)
+    alpha = 2.5
 
     def __init__(self, env_id: str, discount_factor: float = 0.99, policy_lr: float = 3e-4,
                  critic_lr: float = 3e-4, exploration_noise: float = 0.1, target_policy_noise: float = 0.2,
                  noise_clip: float = 0.5, policy_freq: int = 2, tau: float = 0.005, use_lap: bool = False,
                  make_nn=None, *, hidden: int = 256, batch_size: int = 256, seed: int | None = None,
-                 device=None, **make_nn_kwargs) -> None:
+                 device=None, offline: bool = False, alpha: float = 2.5, **make_nn_kwargs) -> None:
+        self.offline = bool(offline)
+        self.alpha = float(alpha)
+        if self.offline:  # (_ext: every engine this agent builds -- _rebuild, pickle, deepcopy, to() -- carries it)
+            self._ext = dict(bc_alpha=self.alpha)
         self.discount_factor = discount_factor
         self.target_policy_noise = target_policy_noise
         self.exploration_noise = exploration_noise
@@ -38,7 +51,9 @@ class TD3(EngineAgent):
                     make_nn_kwargs=make_nn_kwargs, cfg=cfg)
 
     def _info_keys(self):
-        return ("train/q_fn", "train/policy", "norm/policy")  # td3.py:226-235
+        keys = ("train/q_fn", "train/policy", "norm/policy")  # td3.py:226-235
+        bc = getattr(self, "_ext", {}).get("bc_alpha", 0.0) > 0  # (the engine's offline programs: two more columns)
+        return keys + ("train/bc", "train/lmbda") if bc else keys
 
     def sample(self, state, deterministic: bool = False, **kwargs):
         """td3.py:114-135: clip(tanh(policy(s)) + exploration_noise * randn, -1, 1) * scale + bias, one

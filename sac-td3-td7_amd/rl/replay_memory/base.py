@@ -50,6 +50,11 @@ class BaseReplayMemory:
 
     LAP = False
     STAGE = 4096  # host rows staged before one batched H2D append
+    # dataset state normalisation (normalize_states): plain attributes, so they travel with pickle, deepcopy and
+    # to() through _host_attrs (class defaults: a replay pickled before they existed loads as not normalised)
+    states_normalized = False
+    state_mean = None
+    state_scale = None
 
     def __init__(self, replay_buffer_size: int, env_id: str | None = None, *, state_dim: int | None = None,
                  action_dim: int | None = None, device: int = 0, **kwargs) -> None:
@@ -132,6 +137,22 @@ class BaseReplayMemory:
 
     def _mark_engine_indices(self, eng) -> None:
         self._ind_src = eng
+
+    # ---- dataset state normalisation ---------------------------------------
+    def normalize_states(self, eps: float = 1e-3):
+        """The TD3+BC recipe, on the device: per-feature mean and population std of ``state`` over the filled
+        rows (rle_replay_state_stats), then ``state`` and ``next_state`` <- ``(x - mean) / (std + eps)``
+        (rle_replay_normalize_states).  Returns ``(mean, std + eps)`` as fp32 arrays -- what
+        ``agent.set_obs_norm`` takes.  A replay is normalised once: a second call raises RuntimeError."""
+        if self.states_normalized:
+            raise RuntimeError("normalize_states: this replay's states are already normalised")
+        self.flush()
+        mean, std = self.dev.state_stats()
+        scale = std + np.float32(eps)
+        self.dev.normalize_states(mean, scale)
+        self.states_normalized = True
+        self.state_mean, self.state_scale = mean, scale
+        return mean, scale
 
     # ---- sampling --------------------------------------------------------
     def sample(self, batch_size: int, use_torch: bool = True):

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""What TD7's offline mode costs (DESIGN.md "Offline TD7"): writes profiles/offline_bench.json.
+"""What the offline modes cost (DESIGN.md "Offline TD7", "Offline TD3"): writes profiles/offline_bench.json
+(--algo td7, the default) or profiles/offline_td3_bench.json (--algo td3).
 
 The flagship shape of bench.py -- TD7 on Humanoid-v4, hidden 256, batch 256, a 1M-row LAP replay -- as two
 engines in one process on one replay each, one online (rle_config bc_lambda 0) and one offline (bc_lambda
@@ -9,7 +10,11 @@ burst's rate, the two medians, their ratio, the spread of the online bursts (wha
 is measured against), the levels per policy / plain step of both, and the offline policy step's levels
 (rle_graph_describe) with the new op in place.
 
-usage: python tools/offline_bench.py [--steps 2000] [--rounds 5] [--warmup 200] [--lmbda 0.1] [--out FILE]
+--algo td3: the same for TD3+BC on bench.py's TD3 shape -- HalfCheetah-v4, hidden 256, batch 256, a 1M-row
+replay -- online (rle_create) against offline (rle_config_ext bc_alpha, --alpha, default 2.5).
+
+usage: python tools/offline_bench.py [--algo td7|td3] [--steps 2000] [--rounds 5] [--warmup 200] [--lmbda 0.1]
+                                     [--alpha 2.5] [--out FILE]
 """
 
 from __future__ import annotations
@@ -25,6 +30,7 @@ sys.path.insert(0, os.path.join(REPO, "sac-td3-td7_amd"))
 
 N_REPLAY = 1_000_000
 S, A, H, B = 376, 17, 256, 256  # Humanoid-v4
+S3, A3 = 17, 6                  # HalfCheetah-v4 (--algo td3)
 
 
 def main():
@@ -33,29 +39,41 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--lmbda", type=float, default=0.1)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "offline_bench.json"))
+    ap.add_argument("--algo", choices=("td7", "td3"), default="td7")
+    ap.add_argument("--alpha", type=float, default=2.5)
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    td3 = args.algo == "td3"
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles", "offline_td3_bench.json" if td3 else "offline_bench.json")
 
     import torch
     from rl import _engine as E
     from rl.nn.layout import init_agent
 
-    nets = init_agent("td7", S, A, H, 123)
+    s_dim, a_dim = (S3, A3) if td3 else (S, A)
+    nets = init_agent(args.algo, s_dim, a_dim, H, 123)
 
-    def engine(lmbda, seed):
-        eng = E.Engine(E.make_config(E.RLE_TD7, S, A, H, B, use_lap=True, seed=111, bc_lambda=lmbda))
+    def engine(weight, seed):
+        if td3:  # (bench.py's TD3 run: no LAP; online through rle_create, offline through rle_create_ext)
+            cfg = E.make_config(E.RLE_TD3, s_dim, a_dim, H, B, use_lap=False, seed=111)
+            eng = E.Engine(cfg, ext=E.make_config_ext(bc_alpha=weight) if weight else None)
+        else:
+            eng = E.Engine(E.make_config(E.RLE_TD7, s_dim, a_dim, H, B, use_lap=True, seed=111, bc_lambda=weight))
         for net, params in nets.items():
             for name, v in params.items():
                 eng.set_param(net, name, v)
-        rep = E.Replay(N_REPLAY, S, A, True, device=0)
+        rep = E.Replay(N_REPLAY, s_dim, a_dim, not td3, device=0)
         rep.fill_random(N_REPLAY, seed=seed)
         eng.bind(rep)
         return eng, rep
 
-    engs = {"online": engine(0.0, 0), "offline": engine(args.lmbda, 0)}
+    engs = {"online": engine(0.0, 0), "offline": engine(args.alpha if td3 else args.lmbda, 0)}
+    what = (f"TD3 HalfCheetah-v4 hidden {H} batch {B} {N_REPLAY} rows" if td3
+            else f"TD7 Humanoid-v4 hidden {H} batch {B} LAP {N_REPLAY} rows")
     res = {"device": torch.cuda.get_device_name(0),
-           "config": f"TD7 Humanoid-v4 hidden {H} batch {B} LAP {N_REPLAY} rows, rle_step_timed({args.steps}) "
-                     f"x {args.rounds} per mode, alternating; offline bc_lambda {args.lmbda}",
+           "config": f"{what}, rle_step_timed({args.steps}) x {args.rounds} per mode, alternating; offline "
+                     + (f"bc_alpha {args.alpha}" if td3 else f"bc_lambda {args.lmbda}"),
            "levels_per_step": {}, "bursts_steps_per_s": {k: [] for k in engs}}
     for k, (eng, _) in engs.items():
         lp, lpl = eng.graph_stats()
@@ -70,7 +88,13 @@ def main():
     res["median_steps_per_s"] = med
     res["offline_over_online"] = round(med["offline"] / med["online"], 4)
     res["online_spread"] = round((max(on) - min(on)) / med["online"], 4)
+    lv = res["levels_per_step"]  # (levels per step pair, policy_freq 2: what one extra level would explain)
+    res["levels_online_over_offline"] = round((lv["online"]["policy"] + lv["online"]["plain"])
+                                              / (lv["offline"]["policy"] + lv["offline"]["plain"]), 4)
     res["offline_policy_step_levels"] = engs["offline"][0].describe(0).splitlines()
+    if td3 and os.path.exists(args.out):  # (tools/replay_norm_bench.py keeps its figures in the same file)
+        with open(args.out) as fh:
+            res.update({k: v for k, v in json.load(fh).items() if k == "normalisation"})
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as fh:
         json.dump(res, fh, indent=1)
