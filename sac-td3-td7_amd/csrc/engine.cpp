@@ -2428,7 +2428,6 @@ struct Engine {
   // input segments xs, recomputed in-tile by the layer after it (prelayer_fwd): one level fewer on
   // the critic and actor chains.  The standalone L0 output stays for its other readers (the
   // weight gradient, the ReLU mask of the input gradient).  RLE_NO_PRELAYER=1: off (tests, A/B).
-  bool pl_src = false;  // (fwd) the layer being built is a pre-layer source
   // minimum tile width of a pre-GEMM consumer: each tile recomputes the actor output layer for its
   // 16 rows, so wider tiles cut that redundant work (A/B, RLE_PRE_TN 16 / 32 / 64: TD3 HalfCheetah
   // 23.37k / 23.79k / 23.91k, TD7 Humanoid 8069 / 8094 / 8060 steps/s)
@@ -2548,17 +2547,82 @@ struct Engine {
     return u;
   }
 
-  View fwd(Prog& pg, const Layer& L, const std::vector<std::vector<View>>& ins, int M, int act, View* pre_out,
-           bool normed, const View* noise = nullptr, int noise_row0 = 0, const std::vector<WSeg>* wsegs = nullptr,
-           const View* bias_ovr = nullptr, const PreUse* pre = nullptr, const Layer* qdot = nullptr,
-           bool pre_n = false, const SacFwdUse* sfu = nullptr) {
+  // Per-call options of the op builders below.  The default value is a plain layer: its output in both images,
+  // tiles as the planner picks them.  A call names what it uses (a null operand leaves that feature off), and a
+  // run of layers built alike shares one const value, so no option outlives the calls it is meant for.
+  struct FwdOpt {
+    View* pre_out = nullptr;  // keep the pre-activation: T image (DX epilogue masks); N (pre_n) only where the
+    bool pre_n = false;       // loss head reads the rows -- 4 scattered stores per lane saved everywhere else
+    bool normed = false;      // AvgL1Norm row partials with the output (consumers apply the norm)
+    const View* noise = nullptr;  // clipped target-policy noise on the rows from noise_row0 on
+    int noise_row0 = 0;
+    const std::vector<WSeg>* wsegs = nullptr;  // one weight block per input segment instead of L's matrix
+    const View* bias_ovr = nullptr;
+    const PreUse* pre = nullptr;    // an input segment computed in-tile (pre-GEMM / pre-layer)
+    const Layer* qdot = nullptr;    // EPI_QDOT: row partials of this H -> 1 layer applied to the output
+    const SacFwdUse* sfu = nullptr;  // EPI_SACFWD: SAC's rsample in the raw head's epilogue
+    // The output's T image is the weight gradients' B operand: forward-only layers (fixed and target networks,
+    // the policy pass through the critics) drop it -- one store per lane and the written-back bytes of each
+    // such layer saved
+    bool t = true;
+    // This layer is also recomputed in-tile by a pre-layer consumer: at most 32-wide tiles keep its reduction
+    // split, so the stored output (the ReLU mask of the input gradient, the weight gradient's operand) is the
+    // same floats as the consumer's copy, whatever the planner widens
+    bool pl_src = false;
+    FwdOpt() {}  // (user-provided, here and below: a default argument inside Engine cannot use the implicit one)
+    FwdOpt& keep_pre(View* z, bool n_image = false) { return pre_out = z, pre_n = n_image, *this; }
+    FwdOpt& norm() { return normed = true, *this; }
+    FwdOpt& noised(const View* e, int row0) { return noise = e, noise_row0 = row0, *this; }
+    FwdOpt& wblocks(const std::vector<WSeg>* w, const View* b) { return wsegs = w, bias_ovr = b, *this; }
+    FwdOpt& pre_gemm(const PreUse* p) { return pre = p, *this; }
+    FwdOpt& q_dot(const Layer* l) { return qdot = l, *this; }
+    FwdOpt& sac_fwd(const SacFwdUse* s) { return sfu = s, *this; }
+    FwdOpt& keep_t(bool on) { return t = on, *this; }
+    FwdOpt& no_t() { return keep_t(false); }
+    FwdOpt& pl_source(bool on) { return pl_src = on, *this; }
+  };
+  struct DxOpt {
+    const View* into = nullptr;    // the output view (default: a new buffer)
+    const View* nb_x = nullptr;    // EPI_NBDOT: the output is g of AvgL1Norm(nb_x), its backward deferred to the DW
+    const PreUse* pre = nullptr;   // a dZ segment computed in-tile
+    const HeadUse* head = nullptr;  // the loss head fused in: A segment 0 is z, not dZ
+    const SacBwdUse* sbu = nullptr;  // EPI_SACBWD: SAC's actor backward as the epilogue
+    // Output images: N for the next input gradient / norm backward, T for the weight gradient.  An output
+    // that only one kind of consumer reads drops the other (its stores and written-back bytes saved).
+    bool n = true, t = true;
+    bool pl_src = false;  // as FwdOpt::pl_src: the pre-layer consumer is the input gradient of the layer before
+    DxOpt() {}
+    DxOpt& out_into(const View* v) { return into = v, *this; }
+    DxOpt& nb_defer(const View* x) { return nb_x = x, *this; }
+    DxOpt& pre_gemm(const PreUse* p) { return pre = p, *this; }
+    DxOpt& head_use(const HeadUse* h) { return head = h, *this; }
+    DxOpt& sac_bwd(const SacBwdUse* s) { return sbu = s, *this; }
+    DxOpt& images(bool n_image, bool t_image) { return n = n_image, t = t_image, *this; }
+    DxOpt& no_t() { return t = false, *this; }
+    DxOpt& pl_source(bool on) { return pl_src = on, *this; }
+  };
+  struct DwOpt {
+    float* gsq = nullptr;    // per-tile grad-square partials of the weights / the bias (dw_gsq_w / dw_gsq_b slots)
+    float* gsq_b = nullptr;
+    const View* nb_x = nullptr;  // kDwNb: dZ is the AvgL1Norm backward of (dz = g, nb_x), applied on load
+    DwOpt() {}
+    DwOpt& gsq_parts(const std::pair<float*, float*>& p) { return gsq = p.first, gsq_b = p.second, *this; }
+    DwOpt& nb_defer(const View* x) { return nb_x = x, *this; }
+  };
+  struct NormBwdOpt {
+    bool n = true, t = true;  // output images, as DxOpt's
+    NormBwdOpt() {}
+    NormBwdOpt& no_t() { return t = false, *this; }
+  };
+
+  View fwd(Prog& pg, const Layer& L, const std::vector<std::vector<View>>& ins, int M, int act, const FwdOpt& o = {}) {
     REQUIRE(ins.size() == L.seg_p.size(), "fwd: input segment count mismatch for " + L.wname);
     REQUIRE(M % kTileM == 0, "fwd: rows must be a multiple of 16");
-    REQUIRE(!wsegs || wsegs->size() == ins.size(), "fwd: one weight block per input segment");
+    REQUIRE(!o.wsegs || o.wsegs->size() == ins.size(), "fwd: one weight block per input segment");
     std::vector<int> rd{L.res}, wr;
-    if (wsegs)
-      for (const WSeg& w : *wsegs) rd.push_back(w.res);
-    if (bias_ovr) rd.push_back(bias_ovr->id);
+    if (o.wsegs)
+      for (const WSeg& w : *o.wsegs) rd.push_back(w.res);
+    if (o.bias_ovr) rd.push_back(o.bias_ovr->id);
     std::vector<int> cuts{0, M};
     for (size_t s = 0; s < ins.size(); ++s) {
       int xo = 0;
@@ -2566,7 +2630,7 @@ struct Engine {
         REQUIRE(v.cols == L.seg_p[s] && v.m.n, "fwd: segment width / image mismatch for " + L.wname);
         xo += v.rows;
         if (xo < M) cuts.push_back(xo);
-        if (pre && (int)s == pre->a.seg) continue;  // computed in-tile
+        if (o.pre && (int)s == o.pre->a.seg) continue;  // computed in-tile
         rd.push_back(v.id);
         if (v.norm) rd.push_back(v.norm_id);
       }
@@ -2575,42 +2639,37 @@ struct Engine {
     std::sort(cuts.begin(), cuts.end());
     cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
     REQUIRE((int)ins.size() <= kMaxSeg, "fwd: too many operand segments");
-    if (pre) {
-      REQUIRE(cuts.size() == 2 && !noise, "fwd: a pre-GEMM consumer is one row piece");
-      rd.insert(rd.end(), pre->rd.begin(), pre->rd.end());
+    if (o.pre) {
+      REQUIRE(cuts.size() == 2 && !o.noise, "fwd: a pre-GEMM consumer is one row piece");
+      rd.insert(rd.end(), o.pre->rd.begin(), o.pre->rd.end());
     }
     const auto tq = choose_tn(M, L.out);
     // (EPI_SACFWD: one tile column holds whole rows; a pre-layer consumer recomputes the first layer
     // per tile, so wider tiles cut that redundant work: RLE_PL_TN, default 64)
-    // (pl_src: this layer is also recomputed in-tile by a pre-layer consumer -- at most 32-wide tiles
-    // keep its reduction split, so the stored output (the ReLU mask of the input gradient, the weight
-    // gradient's operand) is the same floats as the consumer's copy, whatever the planner widens)
-    // (a pre-GEMM consumer that is also a pre-layer source: at most 32 wide, as any pl_src)
-    const int tn = sfu ? 64
-                       : (pre && (pre->kind == 3 || pre->kind == 4) ? std::max(tq.first, pl_tn())
-                          : pre && (pre->kind == 1 || pre->kind == 5)
-                              ? (pl_src ? std::min(std::max(tq.first, pre_tn()), 32) : std::max(tq.first, pre_tn()))
-                                                  : (pl_src ? std::min(tq.first, 32) : tq.first));
+    // (a pre-GEMM consumer that is also a pre-layer source: at most 32 wide, as any FwdOpt::pl_src)
+    const int tn = o.sfu ? 64
+                       : (o.pre && (o.pre->kind == 3 || o.pre->kind == 4) ? std::max(tq.first, pl_tn())
+                          : o.pre && (o.pre->kind == 1 || o.pre->kind == 5)
+                              ? (o.pl_src ? std::min(std::max(tq.first, pre_tn()), 32) : std::max(tq.first, pre_tn()))
+                                                  : (o.pl_src ? std::min(tq.first, 32) : tq.first));
     // 64-row LDS-staged tiles (rle_plan wide): every row piece whole 64-row blocks, 64-column blocks
-    bool wide = plan.wide && !sfu && !pre && !noise && L.out % plan.wide == 0;
+    bool wide = plan.wide && !o.sfu && !o.pre && !o.noise && L.out % plan.wide == 0;
     for (size_t ci = 0; wide && ci + 1 < cuts.size(); ++ci) wide = (cuts[ci + 1] - cuts[ci]) % 64 == 0;
     const int tn_w = wide ? plan.wide : tn;
     const int tiles_n = cdiv(L.out, tn_w);
-    View out = buf(M, L.out, true, out_t);
-    if (sfu) {
-      REQUIRE(!pre && !qdot && !normed && !noise && act == ACT_NONE && L.out <= 64, "fwd: SAC forward epilogue");
-      rd.insert(rd.end(), sfu->rd.begin(), sfu->rd.end());
-      wr.insert(wr.end(), sfu->wr.begin(), sfu->wr.end());
+    View out = buf(M, L.out, true, o.t);
+    if (o.sfu) {
+      REQUIRE(!o.pre && !o.qdot && !o.normed && !o.noise && act == ACT_NONE && L.out <= 64, "fwd: SAC forward epilogue");
+      rd.insert(rd.end(), o.sfu->rd.begin(), o.sfu->rd.end());
+      wr.insert(wr.end(), o.sfu->wr.begin(), o.sfu->wr.end());
     }
     wr.push_back(out.id);
-    if (pre_out) {
-      // T: DX epilogue masks; N (pre_n) only where the loss head reads the rows: 4 scattered
-      // stores per lane saved everywhere else
-      *pre_out = buf(M, L.out, pre_n, true);
-      wr.push_back(pre_out->id);
+    if (o.pre_out) {
+      *o.pre_out = buf(M, L.out, o.pre_n, true);
+      wr.push_back(o.pre_out->id);
     }
     float* part = nullptr;
-    if (normed) {
+    if (o.normed) {
       part = mem.make<float>((size_t)tiles_n * M);
       out.norm = part;
       out.norm_ld = M;
@@ -2621,9 +2680,10 @@ struct Engine {
       wr.push_back(out.norm_id);
     }
     float* qpart = nullptr;
-    if (qdot) {  // EPI_QDOT: row partials of the H -> 1 layer qdot applied to this output
+    if (o.qdot) {  // EPI_QDOT: row partials of the H -> 1 layer qdot applied to this output
       // (qdot->K is the padded width: the kernel zeroes the weights of the columns past L.out, j < N)
-      REQUIRE(!normed && qdot->out == 1 && qdot->K == r16(L.out) && (act == ACT_ELU || act == ACT_RELU || act == ACT_NONE),
+      REQUIRE(!o.normed && o.qdot->out == 1 && o.qdot->K == r16(L.out) &&
+                  (act == ACT_ELU || act == ACT_RELU || act == ACT_NONE),
               "fwd: q-dot partial layout");
       qpart = mem.make<float>((size_t)tiles_n * M);
       out.qd = qpart;
@@ -2631,9 +2691,9 @@ struct Engine {
       out.qd_n = tiles_n;
       out.qd_id = next_id++;
       wr.push_back(out.qd_id);
-      rd.push_back(qdot->res);
+      rd.push_back(o.qdot->res);
     }
-    if (noise) rd.push_back(noise->id);
+    if (o.noise) rd.push_back(o.noise->id);
     std::vector<Op> ops;
     for (size_t ci = 0; ci + 1 < cuts.size(); ++ci) {
       const int ra = cuts[ci], rb = cuts[ci + 1], m = rb - ra;
@@ -2655,7 +2715,7 @@ struct Engine {
         koff += L.seg_p[s];
       }
       g.A.nseg = (int)ins.size();
-      if (!wsegs) {
+      if (!o.wsegs) {
         Seg w{};
         w.p = P + L.wn_off;
         w.xs = L.cb;
@@ -2668,8 +2728,8 @@ struct Engine {
       } else {  // one weight block per input segment, paired like a DX operand
         for (size_t q = 0; q < ins.size(); ++q) {
           Seg w{};
-          w.p = (*wsegs)[q].p;
-          w.xs = (*wsegs)[q].xs;
+          w.p = (*o.wsegs)[q].p;
+          w.xs = (*o.wsegs)[q].xs;
           w.x0 = 0;
           w.x1 = L.out;
           w.r0 = g.A.seg[q].r0;
@@ -2688,35 +2748,35 @@ struct Engine {
       g.epi = EPI_STORE;
       g.act = act;
       g.out = out.sub(ra, m).m;
-      g.bias = bias_ovr ? bias_ovr->p : bias(L);
-      if (pre_out) g.pre = pre_out->sub(ra, m).m;
-      if (normed) {
+      g.bias = o.bias_ovr ? o.bias_ovr->p : bias(L);
+      if (o.pre_out) g.pre = o.pre_out->sub(ra, m).m;
+      if (o.normed) {
         g.norm_out = part + ra;
         g.norm_ld = M;
       }
-      if (sfu) {
+      if (o.sfu) {
         REQUIRE(cuts.size() == 2, "fwd: SAC forward epilogue over one row piece");
         g.epi = EPI_SACFWD;
-        g.sf = sfu->a;
+        g.sf = o.sfu->a;
       }
-      if (qdot) {
+      if (o.qdot) {
         g.epi = EPI_QDOT;
-        g.qw = P + qdot->wn_off;
-        g.qw_cbn = qdot->cb;
+        g.qw = P + o.qdot->wn_off;
+        g.qw_cbn = o.qdot->cb;
         g.norm_out = qpart + ra;
         g.norm_ld = M;
       }
-      if (noise && rb > noise_row0) {
-        const int first = std::max(ra, noise_row0);  // first noised row (global)
-        g.noise = noise->sub(first - noise_row0, rb - first).m;
+      if (o.noise && rb > o.noise_row0) {
+        const int first = std::max(ra, o.noise_row0);  // first noised row (global)
+        g.noise = o.noise->sub(first - o.noise_row0, rb - first).m;
         g.noise_row0 = first - ra;
         g.noise_sigma = cfg.target_policy_noise;
         g.noise_clip = cfg.noise_clip;
       }
-      if (pre) {
-        g.has_pre = pre->kind;
-        g.prea = pre->a;
-        if (pre->kind == 4) g.prea2 = pre->a2;
+      if (o.pre) {
+        g.has_pre = o.pre->kind;
+        g.prea = o.pre->a;
+        if (o.pre->kind == 4) g.prea2 = o.pre->a2;
       }
       op.wg_count = (wide ? g.tiles_m / 4 : g.tiles_m) * g.tiles_n;
       op.seq = tq.second;
@@ -2726,12 +2786,10 @@ struct Engine {
     return out;
   }
 
-
   // dX[:, 0:ncols] = sum_t dZ_t W_t[:, col0_t : col0_t + ncols]  (* act'(saved))
   View dx(Prog& pg, const std::vector<DxTerm>& terms, int ncols, int M, int dact, const View* saved,
-          const View* into = nullptr, const View* nb_x = nullptr, const PreUse* pre = nullptr,
-          const HeadUse* head = nullptr, const SacBwdUse* sbu = nullptr) {
-    if (dact == ACT_NONE && !pre && !head) saved = nullptr;  // (an identity layer's backward reads no derivative)
+          const DxOpt& o = {}) {
+    if (dact == ACT_NONE && !o.pre && !o.head) saved = nullptr;  // (an identity layer's backward reads no derivative)
     Op op{};
     op.kind = OP_GEMM;
     GemmArgs& g = op.gemm;
@@ -2758,7 +2816,7 @@ struct Engine {
       b.r1 = roff + wout;
       g.B.seg[t] = b;
       roff += r16(wout);
-      if (!(pre && (int)t == pre->a.seg)) rd.push_back(tm.dz.id);  // (else computed in-tile)
+      if (!(o.pre && (int)t == o.pre->a.seg)) rd.push_back(tm.dz.id);  // (else computed in-tile)
       rd.push_back(tm.L ? tm.L->res : tm.wv->id);
     }
     g.A.nseg = g.B.nseg = (int)terms.size();
@@ -2766,24 +2824,24 @@ struct Engine {
     g.N = ncols;
     g.R = roff;
     const auto tq = choose_tn(M, ncols);
-    g.tn = pre && pre->kind == 3 ? std::max(tq.first, pl_tn())
-           : pre && pre->kind == 1 ? std::max(tq.first, pre_tn())
-                                   : (pl_src ? std::min(tq.first, 32) : tq.first);
+    g.tn = o.pre && o.pre->kind == 3 ? std::max(tq.first, pl_tn())
+           : o.pre && o.pre->kind == 1 ? std::max(tq.first, pre_tn())
+                                   : (o.pl_src ? std::min(tq.first, 32) : tq.first);
     op.seq = tq.second;
     // 64-row LDS-staged tiles (rle_plan wide): a plain or EPI_NBDOT input gradient over whole 64-row blocks
-    const bool wide = plan.wide && !pre && !head && !sbu && M % 64 == 0 && ncols % plan.wide == 0;
+    const bool wide = plan.wide && !o.pre && !o.head && !o.sbu && M % 64 == 0 && ncols % plan.wide == 0;
     if (wide) g.tn = plan.wide;
     g.hot.wide = wide ? plan.wide : 0;
     g.tiles_m = cdiv(M, kTileM);
     g.tiles_n = cdiv(ncols, g.tn);
     g.epi = EPI_STORE;
     g.act = ACT_NONE;
-    View out = into ? *into : buf(M, ncols, out_n, out_t);
-    if (nb_x) {  // out = g of AvgL1Norm(x): row partials of sum_j g x for the consuming DW (kDwNb)
-      REQUIRE(!saved && nb_x->norm && nb_x->m.t && nb_x->rows == M && nb_x->cols == r16(ncols),
+    View out = o.into ? *o.into : buf(M, ncols, o.n, o.t);
+    if (o.nb_x) {  // out = g of AvgL1Norm(x): row partials of sum_j g x for the consuming DW (kDwNb)
+      REQUIRE(!saved && o.nb_x->norm && o.nb_x->m.t && o.nb_x->rows == M && o.nb_x->cols == r16(ncols),
               "dx: deferred AvgL1Norm backward operands");
       g.epi = EPI_NBDOT;
-      g.nbx = nb_x->m;
+      g.nbx = o.nb_x->m;
       float* part = mem.make<float>((size_t)cdiv(ncols, kTileM) * M);  // any tile plan fits
       g.norm_out = part;
       g.norm_ld = M;
@@ -2792,9 +2850,9 @@ struct Engine {
       out.nbdot_n = g.tiles_n;
       out.nbdot_id = next_id++;
       wr.push_back(out.nbdot_id);
-      rd.push_back(nb_x->id);
+      rd.push_back(o.nb_x->id);
     }
-    REQUIRE(!into || (into->rows == M && into->cols == r16(ncols)), "dx: output view shape");
+    REQUIRE(!o.into || (o.into->rows == M && o.into->cols == r16(ncols)), "dx: output view shape");
     g.out = out.m;
     if (saved) {
       REQUIRE(saved->m.t, "dx: derivative source needs a T image");
@@ -2803,29 +2861,33 @@ struct Engine {
       rd.push_back(saved->id);
     }
     wr.push_back(out.id);
-    if (pre) {
-      g.has_pre = pre->kind;
-      g.prea = pre->a;
-      rd.insert(rd.end(), pre->rd.begin(), pre->rd.end());
+    if (o.pre) {
+      g.has_pre = o.pre->kind;
+      g.prea = o.pre->a;
+      rd.insert(rd.end(), o.pre->rd.begin(), o.pre->rd.end());
     }
-    if (head) {  // A segment 0 is z of critic head->n's last hidden layer, not dZ
+    if (o.head) {  // A segment 0 is z of critic o.head->n's last hidden layer, not dZ
       g.has_pre = 2;
-      g.hd = head->h;
-      g.head_n = head->n;
-      rd.insert(rd.end(), head->rd.begin(), head->rd.end());
-      wr.insert(wr.end(), head->wr.begin(), head->wr.end());
+      g.hd = o.head->h;
+      g.head_n = o.head->n;
+      rd.insert(rd.end(), o.head->rd.begin(), o.head->rd.end());
+      wr.insert(wr.end(), o.head->wr.begin(), o.head->wr.end());
     }
-    if (sbu) {  // the output is sbu->a.dout (d / d(mean | log_std)), not da
-      REQUIRE(!head && !pre && !nb_x && !saved, "dx: SAC backward epilogue is a plain DX");
+    if (o.sbu) {  // the output is o.sbu->a.dout (d / d(mean | log_std)), not da
+      REQUIRE(!o.head && !o.pre && !o.nb_x && !saved, "dx: SAC backward epilogue is a plain DX");
       g.epi = EPI_SACBWD;
       g.out = Mat{};
-      g.sb = sbu->a;
-      rd.insert(rd.end(), sbu->rd.begin(), sbu->rd.end());
-      wr.insert(wr.end(), sbu->wr.begin(), sbu->wr.end());
+      g.sb = o.sbu->a;
+      rd.insert(rd.end(), o.sbu->rd.begin(), o.sbu->rd.end());
+      wr.insert(wr.end(), o.sbu->wr.begin(), o.sbu->wr.end());
     }
     op.wg_count = (wide ? g.tiles_m / 4 : g.tiles_m) * g.tiles_n;
     pg.add(op, rd, wr);
     return out;
+  }
+  // (through an identity layer: no derivative to read)
+  View dx(Prog& pg, const std::vector<DxTerm>& terms, int ncols, int M, const DxOpt& o = {}) {
+    return dx(pg, terms, ncols, M, ACT_NONE, nullptr, o);
   }
 
   // Tile width of the next GEMM op: from the plan of a previous build pass
@@ -2845,7 +2907,8 @@ struct Engine {
 
   // dW = dZ^T [X], db = sum dZ, fused Adam (torch.optim.Adam law).
   void dw(Prog& pg, const Layer& L, const View& dz, const std::vector<View>& X, int Brows, int cnt, float lr,
-          float* gsq = nullptr, float* gsq_b = nullptr, const View* nb_x = nullptr) {
+          const DwOpt& o = {}) {
+    const View* const nb_x = o.nb_x;
     REQUIRE(X.size() == L.seg_p.size(), "dw: input count mismatch for " + L.wname);
     REQUIRE(dz.m.t, "dw: dZ needs a T image");
     Op op{};
@@ -2900,8 +2963,8 @@ struct Engine {
     ad.omb2 = (float)(1.0 - 0.999);
     ad.eps = 1e-8f;
     ad.bias_col = cdiv(L.K, g.tn) * g.tn;
-    ad.gsq = gsq;
-    ad.gsq_b = gsq_b;
+    ad.gsq = o.gsq;
+    ad.gsq_b = o.gsq_b;
     ad.ptau = adam_ptau;
     if (nb_x) {  // dZ = AvgL1Norm backward of (dz = g, x), applied on load (kDwNb)
       REQUIRE(dz.nbdot && nb_x->norm && nb_x->m.t && nb_x->rows >= Brows, "dw: deferred AvgL1Norm backward operands");
@@ -2972,13 +3035,13 @@ struct Engine {
     return {r, it->second.second};
   }
 
-  View normbwd(Prog& pg, const View& gv, const View& x) {
+  View normbwd(Prog& pg, const View& gv, const View& x, const NormBwdOpt& o = {}) {
     REQUIRE(x.norm, "normbwd: x is not a normed view");
     REQUIRE(gv.m.n && x.m.n && gv.rows % 16 == 0, "normbwd: operand layout");
     Op op{};
     op.kind = OP_NORMBWD;
     NormBwdArgs& a = op.nb;
-    View out = buf(gv.rows, x.width, out_n, out_t);
+    View out = buf(gv.rows, x.width, o.n, o.t);
     a.g = gv.m;
     a.x = x.m;
     a.dx = out.m;
@@ -3012,24 +3075,70 @@ struct Engine {
 
   // SALEEncoder.encode_state (sale.py:41-46): a normed view (consumers apply the norm).
   View enc_zs(Prog& pg, Net& E, const View& s, int M) {
-    View h1 = fwd(pg, E.layers[0], {{s}}, M, actE, nullptr, false);
-    View h2 = fwd(pg, E.layers[1], {{h1}}, M, actE, nullptr, false);
-    return fwd(pg, E.layers[2], {{h2}}, M, ACT_NONE, nullptr, true);
+    View h1 = fwd(pg, E.layers[0], {{s}}, M, actE);
+    View h2 = fwd(pg, E.layers[1], {{h1}}, M, actE);
+    return fwd(pg, E.layers[2], {{h2}}, M, ACT_NONE, FwdOpt().norm());
   }
   // SALEEncoder.encode_state_action (sale.py:48-55).
   View enc_zsa(Prog& pg, Net& E, const View& zs, const View& a, int M) {
-    View a1 = fwd(pg, E.layers[3], {{zs}, {a}}, M, actE, nullptr, false);
-    View a2 = fwd(pg, E.layers[4], {{a1}}, M, actE, nullptr, false);
-    return fwd(pg, E.layers[5], {{a2}}, M, ACT_NONE, nullptr, false);
+    View a1 = fwd(pg, E.layers[3], {{zs}, {a}}, M, actE);
+    View a2 = fwd(pg, E.layers[4], {{a1}}, M, actE);
+    return fwd(pg, E.layers[5], {{a2}}, M, ACT_NONE);
   }
 
   // make_mlp forward (mlp.py:24-35): `act` (action_fn) after every hidden layer, `last` after the output layer.
   View mlp_fwd(Prog& pg, Net& N, const std::vector<std::vector<View>>& in, int M, int last, int act) {
     View h;
     for (size_t i = 0; i < N.layers.size(); ++i)
-      h = fwd(pg, N.layers[i], i ? std::vector<std::vector<View>>{{h}} : in, M,
-              i + 1 == N.layers.size() ? last : act, nullptr, false);
+      h = fwd(pg, N.layers[i], i ? std::vector<std::vector<View>>{{h}} : in, M, i + 1 == N.layers.size() ? last : act);
     return h;
+  }
+
+  // The policy forward of the engine's algorithm on the rows `in`; returns the head's output.  TD7: the fixed
+  // encoder, then the policy on (s, zs) (td7.py:158-162).  TD3 / SAC: make_mlp, whose output layer gets `mlp_last`
+  // (raw for rle_act and SAC's rsample, tanh for TD3's act-sample epilogue).
+  View policy_fwd(Prog& pg, const View& in, int M, int mlp_last) {
+    Net& pi = net("policy");
+    if (algo != RLE_TD7) return mlp_fwd(pg, pi, {{in}}, M, mlp_last, actP);
+    View zs = enc_zs(pg, net("fixed_encoder"), in, M);
+    View p0 = fwd(pg, pi.layers[0], {{in}}, M, ACT_NONE, FwdOpt().norm());
+    View p1 = fwd(pg, pi.layers[1], {{p0}, {zs}}, M, actP);
+    View p2 = fwd(pg, pi.layers[2], {{p1}}, M, actP);
+    return fwd(pg, pi.layers[3], {{p2}}, M, ACT_TANH);
+  }
+  // A program outside step(): the forward entry points and the diagnostics.  (Prog::xcd keeps its default in
+  // these; rle_plan.xcd reaches the step programs only.)
+  Prog aux_prog() const { return Prog{}; }
+  // The ActArgs of an act-sample program over n rows: its pinned buffers, the action map, and a Philox stream
+  // of its own, not the step's
+  ActArgs act_args(const ActSample& as, int n) {
+    ActArgs ao{};
+    HIPCHK(hipHostGetDevicePointer((void**)&ao.out, as.out, 0));
+    HIPCHK(hipHostGetDevicePointer((void**)&ao.ctl, as.ctl, 0));
+    HIPCHK(hipHostGetDevicePointer((void**)&ao.eps, as.eps, 0));
+    ao.scale = act_map;
+    ao.bias = act_map + A;
+    ao.sigma = act_map + 2 * A;
+    ao.n = n;
+    ao.A = A;
+    ao.seed = cfg.seed * 0x9E3779B97F4A7C15ull + 0x5851F42D4C957F2Dull;
+    return ao;
+  }
+  // An OP_SAC_ACTOR / OP_SAC_ACTOR_BWD op over `rows` rows of the raw head output (mean | log_std): the fields
+  // every use shares.  The caller adds its eps, act and logpi (or gradient) operands.
+  Op sac_actor_op(int kind, const Mat& raw, int rows) {
+    Op op{};
+    op.kind = kind;
+    SacActorArgs& a = op.sac;
+    a.out = raw;
+    a.A = A;
+    a.rows = rows;
+    a.min_log_std = cfg.min_log_std;
+    a.max_log_std = cfg.max_log_std;
+    a.mean_off = 0;
+    a.ls_off = A;
+    op.wg_count = cdiv(rows, kThreads);
+    return op;
   }
 
   // Host rows [n][w] into every kept image of v (rows past n and columns past w stay zero).
@@ -3325,13 +3434,13 @@ struct Engine {
     View s = ss.sub(0, B), s2 = ss.sub(B, B);
     // ---- encoder phase (td7.py:246-257): online encoder on [s; s'] (one GEMM per layer)
     View ez1, ez2;
-    View eh1 = fwd(pg, enc.layers[0], {{ss}}, B2, actE, &ez1, false);
-    View eh2 = fwd(pg, enc.layers[1], {{eh1}}, B2, actE, &ez2, false);
-    View ex3 = fwd(pg, enc.layers[2], {{eh2}}, B2, ACT_NONE, nullptr, true);
+    View eh1 = fwd(pg, enc.layers[0], {{ss}}, B2, actE, FwdOpt().keep_pre(&ez1));
+    View eh2 = fwd(pg, enc.layers[1], {{eh1}}, B2, actE, FwdOpt().keep_pre(&ez2));
+    View ex3 = fwd(pg, enc.layers[2], {{eh2}}, B2, ACT_NONE, FwdOpt().norm());
     View ezs = ex3.sub(0, B), ezs2 = ex3.sub(B, B);
     View ea1z, ea2z;
-    View ea1 = fwd(pg, enc.layers[3], {{ezs}, {act_in}}, B, actE, &ea1z, false);
-    View ea2 = fwd(pg, enc.layers[4], {{ea1}}, B, actE, &ea2z, false);
+    View ea1 = fwd(pg, enc.layers[3], {{ezs}, {act_in}}, B, actE, FwdOpt().keep_pre(&ea1z));
+    View ea2 = fwd(pg, enc.layers[4], {{ea1}}, B, actE, FwdOpt().keep_pre(&ea2z));
     // zsa3 + MSE gradient vs zs_next (normed) fused
     View ed3;
     float* enc_loss = nullptr;
@@ -3381,9 +3490,7 @@ struct Engine {
       dw(pg, enc.layers[5], ed3, {ea2}, B, CNT_ADAM_ENC, cfg.policy_lr);
       View d1 = dx(pg, {{d2, &enc.layers[4], 0}}, H, B, actE, &ea1z);
       dw(pg, enc.layers[4], d2, {ea1}, B, CNT_ADAM_ENC, cfg.policy_lr);
-      out_t = false;  // (read by the norm backward only)
-      View gzs = dx(pg, {{d1, &enc.layers[3], 0}}, Z, B, ACT_NONE, nullptr);
-      out_t = true;
+      View gzs = dx(pg, {{d1, &enc.layers[3], 0}}, Z, B, DxOpt().no_t());  // (read by the norm backward only)
       dw(pg, enc.layers[3], d1, {ezs, act_in}, B, CNT_ADAM_ENC, cfg.policy_lr);
       View dx3 = normbwd(pg, gzs, ex3.sub(0, B));
       View ez2s = ez2.sub(0, B), ez1s = ez1.sub(0, B);
@@ -3394,68 +3501,64 @@ struct Engine {
       dw(pg, enc.layers[0], dh1, {s}, B, CNT_ADAM_ENC, cfg.policy_lr);
     }
     // ---- fixed encoder on s, fixed target encoder on s'
-    out_t = false;  // forward-only outputs (no weight gradient reads them)
-    View fh1 = fwd(pg, fe.layers[0], {{s}}, B, actE, nullptr, false);
-    View fh2 = fwd(pg, fe.layers[1], {{fh1}}, B, actE, nullptr, false);
-    out_t = true;
-    View fzs = fwd(pg, fe.layers[2], {{fh2}}, B, ACT_NONE, nullptr, true);
-    out_t = false;
-    View th1 = fwd(pg, fet.layers[0], {{s2}}, B, actE, nullptr, false);
-    View th2 = fwd(pg, fet.layers[1], {{th1}}, B, actE, nullptr, false);
-    View tzs = fwd(pg, fet.layers[2], {{th2}}, B, ACT_NONE, nullptr, true);
-    View fa1 = fwd(pg, fe.layers[3], {{fzs}, {act_in}}, B, actE, nullptr, false);
-    View fa2 = fwd(pg, fe.layers[4], {{fa1}}, B, actE, nullptr, false);
-    out_t = true;
-    View fzsa = fwd(pg, fe.layers[5], {{fa2}}, B, ACT_NONE, nullptr, false);
+    // forward-only outputs (no weight gradient reads them); fzs and fzsa, which the critics' and the actor's
+    // weight gradients read, keep both images
+    const FwdOpt fo = FwdOpt().no_t();
+    View fh1 = fwd(pg, fe.layers[0], {{s}}, B, actE, fo);
+    View fh2 = fwd(pg, fe.layers[1], {{fh1}}, B, actE, fo);
+    View fzs = fwd(pg, fe.layers[2], {{fh2}}, B, ACT_NONE, FwdOpt().norm());
+    View th1 = fwd(pg, fet.layers[0], {{s2}}, B, actE, fo);
+    View th2 = fwd(pg, fet.layers[1], {{th1}}, B, actE, fo);
+    View tzs = fwd(pg, fet.layers[2], {{th2}}, B, ACT_NONE, FwdOpt(fo).norm());
+    View fa1 = fwd(pg, fe.layers[3], {{fzs}, {act_in}}, B, actE, fo);
+    View fa2 = fwd(pg, fe.layers[4], {{fa1}}, B, actE, fo);
+    View fzsa = fwd(pg, fe.layers[5], {{fa2}}, B, ACT_NONE);
     // ---- actor on [s; s'] (target policy aliases the policy, Q1)
-    View ap0 = fwd(pg, pi.layers[0], {{ss}}, B2, ACT_NONE, nullptr, true);
+    View ap0 = fwd(pg, pi.layers[0], {{ss}}, B2, ACT_NONE, FwdOpt().norm());
     // (an ELU actor keeps its pre-activations for the policy backward: ELU' = exp(z))
     View ap1z, ap2z;
-    View ap1 = fwd(pg, pi.layers[1], {{ap0}, {fzs, tzs}}, B2, actP, actP == ACT_ELU ? &ap1z : nullptr, false);
-    View ap2 = fwd(pg, pi.layers[2], {{ap1}}, B2, actP, actP == ACT_ELU ? &ap2z : nullptr, false);
+    const bool pz = actP == ACT_ELU;
+    View ap1 = fwd(pg, pi.layers[1], {{ap0}, {fzs, tzs}}, B2, actP, FwdOpt().keep_pre(pz ? &ap1z : nullptr));
+    View ap2 = fwd(pg, pi.layers[2], {{ap1}}, B2, actP, FwdOpt().keep_pre(pz ? &ap2z : nullptr));
     // a' = clamp(pi(s', zs') + noise) only feeds the target branch's first layers, which
     // recompute it in-tile (pre-GEMM): the actor output layer runs on the s rows alone
     const bool prea = actor_pre();
-    View actv = prea ? fwd(pg, pi.layers[3], {{ap2.sub(0, B)}}, B, ACT_TANH, nullptr, false)
-                     : fwd(pg, pi.layers[3], {{ap2}}, B2, ACT_TANH, nullptr, false, &eps, B);
+    View actv = prea ? fwd(pg, pi.layers[3], {{ap2.sub(0, B)}}, B, ACT_TANH)
+                     : fwd(pg, pi.layers[3], {{ap2}}, B2, ACT_TANH, FwdOpt().noised(&eps, B));
     View a_pi = actv.sub(0, B), a_next = prea ? a_pi : actv.sub(B, B);  // (pre: layout only)
     const View ap2n = ap2.sub(B, B);
     const PreUse pn1 = prea ? pre_actor_fwd(pi.layers[3], ap2n, &eps, 1) : PreUse{};
     const PreUse* pnext = prea ? &pn1 : nullptr;
-    // ---- target: zsa' and target critics (forward only)
-    out_t = false;
-    View ta1 = fwd(pg, fet.layers[3], {{tzs}, {a_next}}, B, actE, nullptr, false, nullptr, 0, nullptr, nullptr, pnext);
-    View ta2 = fwd(pg, fet.layers[4], {{ta1}}, B, actE, nullptr, false);
+    // ---- target: zsa' and target critics (forward only: fo)
+    View ta1 = fwd(pg, fet.layers[3], {{tzs}, {a_next}}, B, actE, FwdOpt(fo).pre_gemm(pnext));
+    View ta2 = fwd(pg, fet.layers[4], {{ta1}}, B, actE, fo);
     // zsa' = zsa3(ta2) only feeds the target critics' first hidden layer, a linear map:
     // with `fold`, tq.q1[:, zsa block] x fet.zsa3 is precomputed (add_target_fold) and the
     // target critics read ta2 directly (one dependent level fewer)
     const bool fold = td7_fold();
     View tzsa;
-    if (!fold) tzsa = fwd(pg, fet.layers[5], {{ta2}}, B, ACT_NONE, nullptr, false);
+    if (!fold) tzsa = fwd(pg, fet.layers[5], {{ta2}}, B, ACT_NONE, fo);
     View th[2];
     for (int n = 0; n < 2; ++n) {
-      View t01 = fwd(pg, tq[n]->layers[0], {{s2}, {a_next}}, B, ACT_NONE, nullptr, true, nullptr, 0, nullptr, nullptr,
-                     pnext);
+      View t01 = fwd(pg, tq[n]->layers[0], {{s2}, {a_next}}, B, ACT_NONE, FwdOpt(fo).norm().pre_gemm(pnext));
       View t1;
       if (fold) {  // fixed_encoder_target.zsa3 folded into the zsa block (tfold_w / tfold_b)
         const Layer& L1 = tq[n]->layers[1];
         const std::vector<WSeg> ws{wblock(L1, 0), {tfold_w[n].m.n, tfold_w[n].m.cbn, tfold_w[n].id},
                                    wblock(L1, L1.seg_p[0] + L1.seg_p[1])};
-        t1 = fwd(pg, L1, {{t01}, {ta2}, {tzs}}, B, actC, nullptr, false, nullptr, 0, &ws, &tfold_b[n]);
+        t1 = fwd(pg, L1, {{t01}, {ta2}, {tzs}}, B, actC, FwdOpt(fo).wblocks(&ws, &tfold_b[n]));
       } else {
-        t1 = fwd(pg, tq[n]->layers[1], {{t01}, {tzsa}, {tzs}}, B, actC, nullptr, false);
+        t1 = fwd(pg, tq[n]->layers[1], {{t01}, {tzsa}, {tzs}}, B, actC, fo);
       }
-      th[n] = fwd(pg, tq[n]->layers[2], {{t1}}, B, actC, nullptr, false, nullptr, 0, nullptr, nullptr, nullptr,
-                  qpart ? &tq[n]->layers[3] : nullptr);
+      th[n] = fwd(pg, tq[n]->layers[2], {{t1}}, B, actC, FwdOpt(fo).q_dot(qpart ? &tq[n]->layers[3] : nullptr));
     }
-    out_t = true;
     // ---- online critics on (s, a, zsa_f, zs_f)
     View c01[2], c1[2], c2[2], c1z[2], c2z[2];
     for (int n = 0; n < 2; ++n) {
-      c01[n] = fwd(pg, q[n]->layers[0], {{s}, {act_in}}, B, ACT_NONE, nullptr, true);
-      c1[n] = fwd(pg, q[n]->layers[1], {{c01[n]}, {fzsa}, {fzs}}, B, actC, &c1z[n], false);
-      c2[n] = fwd(pg, q[n]->layers[2], {{c1[n]}}, B, actC, &c2z[n], false, nullptr, 0, nullptr, nullptr, nullptr,
-                  qpart ? &q[n]->layers[3] : nullptr, true);
+      c01[n] = fwd(pg, q[n]->layers[0], {{s}, {act_in}}, B, ACT_NONE, FwdOpt().norm());
+      c1[n] = fwd(pg, q[n]->layers[1], {{c01[n]}, {fzsa}, {fzs}}, B, actC, FwdOpt().keep_pre(&c1z[n]));
+      c2[n] = fwd(pg, q[n]->layers[2], {{c1[n]}}, B, actC,
+                  FwdOpt().keep_pre(&c2z[n], true).q_dot(qpart ? &q[n]->layers[3] : nullptr));
     }
     const bool hdx = td7_headdx() && qpart;  // (the fused head reads q partials only)
     // (dZ of the critics' last hidden layers: with the fused head only their weight gradients
@@ -3519,7 +3622,7 @@ struct Engine {
                      {dz2[n].id, dq[n].id}};
           if (n == 0) hu.wr.insert(hu.wr.end(), {prio.id, qloss_id, R_VKEYS});
           hu.rd.insert(hu.rd.end(), qrd.begin(), qrd.end());
-          d1f[n] = dx(pg, {{c2z[n], &q[n]->layers[2], 0}}, H, B, actC, &c1z[n], nullptr, nullptr, nullptr, &hu);
+          d1f[n] = dx(pg, {{c2z[n], &q[n]->layers[2], 0}}, H, B, actC, &c1z[n], DxOpt().head_use(&hu));
         }
       }
     }
@@ -3529,12 +3632,11 @@ struct Engine {
       dw(pg, Q.layers[3], dq[n], {c2[n]}, B, CNT_ADAM_Q, cfg.critic_lr);
       View d1 = hdx ? d1f[n] : dx(pg, {{dz2[n], &Q.layers[2], 0}}, H, B, actC, &c1z[n]);
       dw(pg, Q.layers[2], dz2[n], {c1[n]}, B, CNT_ADAM_Q, cfg.critic_lr);
-      (nbd ? out_n : out_t) = false;  // (read by the weight gradient / the norm backward only)
-      View g01 = dx(pg, {{d1, &Q.layers[1], 0}}, H, B, ACT_NONE, nullptr, nullptr, nbd ? &c01[n] : nullptr);
-      out_n = out_t = true;
+      // (read by the weight gradient / the norm backward only: the T / the N image alone)
+      View g01 = dx(pg, {{d1, &Q.layers[1], 0}}, H, B, DxOpt().nb_defer(nbd ? &c01[n] : nullptr).images(!nbd, nbd));
       dw(pg, Q.layers[1], d1, {c01[n], fzsa, fzs}, B, CNT_ADAM_Q, cfg.critic_lr);
       if (nbd) {  // AvgL1Norm backward deferred into the weight-gradient GEMM (kDwNb)
-        dw(pg, Q.layers[0], g01, {s, act_in}, B, CNT_ADAM_Q, cfg.critic_lr, nullptr, nullptr, &c01[n]);
+        dw(pg, Q.layers[0], g01, {s, act_in}, B, CNT_ADAM_Q, cfg.critic_lr, DwOpt().nb_defer(&c01[n]));
       } else {
         View dx01 = normbwd(pg, g01, c01[n]);
         dw(pg, Q.layers[0], dx01, {s, act_in}, B, CNT_ADAM_Q, cfg.critic_lr);
@@ -3543,16 +3645,14 @@ struct Engine {
     ploss_part = nullptr;
     if (policy) {  // td7.py:259-276 with the updated critics (no weight gradient of these layers)
       View pa1z, pa2z;
-      out_t = false;
-      View pa1 = fwd(pg, fe.layers[3], {{fzs}, {a_pi}}, B, actE, &pa1z, false);
-      View pa2 = fwd(pg, fe.layers[4], {{pa1}}, B, actE, &pa2z, false);
-      View pzsa = fwd(pg, fe.layers[5], {{pa2}}, B, ACT_NONE, nullptr, false);
+      View pa1 = fwd(pg, fe.layers[3], {{fzs}, {a_pi}}, B, actE, FwdOpt(fo).keep_pre(&pa1z));
+      View pa2 = fwd(pg, fe.layers[4], {{pa1}}, B, actE, FwdOpt(fo).keep_pre(&pa2z));
+      View pzsa = fwd(pg, fe.layers[5], {{pa2}}, B, ACT_NONE, fo);
       View p01[2], p1[2], p1z[2], dzp2[2];
       for (int n = 0; n < 2; ++n) {
-        p01[n] = fwd(pg, q[n]->layers[0], {{s}, {a_pi}}, B, ACT_NONE, nullptr, true);
-        p1[n] = fwd(pg, q[n]->layers[1], {{p01[n]}, {pzsa}, {fzs}}, B, actC, &p1z[n], false);
+        p01[n] = fwd(pg, q[n]->layers[0], {{s}, {a_pi}}, B, ACT_NONE, FwdOpt(fo).norm());
+        p1[n] = fwd(pg, q[n]->layers[1], {{p01[n]}, {pzsa}, {fzs}}, B, actC, FwdOpt(fo).keep_pre(&p1z[n]));
       }
-      out_t = true;
       // q2 + q3 + dL/dQ = -1/(2B) fused (EPI_QHEAD): dZ of q2 straight from the GEMM
       ploss_id = next_id++;  // one loss resource per critic: the two heads share a level
       ploss_id2 = next_id++;
@@ -3594,11 +3694,8 @@ struct Engine {
           pg.add(op, {a_pi.id, act_in.id}, {bc_e.id, bc_part_id});
         }
         View pq[2];
-        out_t = false;
         for (int n = 0; n < 2; ++n)
-          pq[n] = fwd(pg, q[n]->layers[2], {{p1[n]}}, B, actC, nullptr, false, nullptr, 0, nullptr, nullptr, nullptr,
-                      &q[n]->layers[3]);
-        out_t = true;
+          pq[n] = fwd(pg, q[n]->layers[2], {{p1[n]}}, B, actC, FwdOpt(fo).q_dot(&q[n]->layers[3]));
         bc_eye = buf(A, A, false, true);
         bc_s = mem.make<float>(4);
         bc_s_id = next_id++;
@@ -3621,30 +3718,24 @@ struct Engine {
         pg.add(op, {pq[0].qd_id, pq[1].qd_id, q[0]->layers[3].res, q[1]->layers[3].res}, {bc_eye.id, bc_s_id});
       }
       View dzp1[2], dxp01[2];
-      out_t = false;  // (no weight gradient of the critics or the fixed encoder in the policy pass)
+      const DxOpt po = DxOpt().no_t();  // (no weight gradient of the critics or the fixed encoder in the policy pass)
       for (int n = 0; n < 2; ++n) {
-        dzp1[n] = dx(pg, {{dzp2[n], &q[n]->layers[2], 0}}, H, B, actC, &p1z[n]);
-        View g = dx(pg, {{dzp1[n], &q[n]->layers[1], 0}}, H, B, ACT_NONE, nullptr);
-        dxp01[n] = normbwd(pg, g, p01[n]);
+        dzp1[n] = dx(pg, {{dzp2[n], &q[n]->layers[2], 0}}, H, B, actC, &p1z[n], po);
+        View g = dx(pg, {{dzp1[n], &q[n]->layers[1], 0}}, H, B, po);
+        dxp01[n] = normbwd(pg, g, p01[n], NormBwdOpt().no_t());
       }
-      out_t = true;
       // grad wrt zsa from both critics (q1 input columns [H, 2H))
       View dpa2;
       if (fold) {  // d zsa -> d pa2 through zsa3 folded: G_n = q_n.q1[:, zsa block] x fe.zsa3 (updated critics)
         View G[2];
         for (int n = 0; n < 2; ++n)
-          G[n] = dx(pg, {{wview_n(q[n]->layers[1], Hp, H), &fe.layers[5], 0}}, H, H, ACT_NONE, nullptr);
-        out_t = false;
-        dpa2 = dx(pg, {{dzp1[0], nullptr, 0, &G[0]}, {dzp1[1], nullptr, 0, &G[1]}}, H, B, actE, &pa2z);
-        out_t = true;
+          G[n] = dx(pg, {{wview_n(q[n]->layers[1], Hp, H), &fe.layers[5], 0}}, H, H);  // (a T-image operand below)
+        dpa2 = dx(pg, {{dzp1[0], nullptr, 0, &G[0]}, {dzp1[1], nullptr, 0, &G[1]}}, H, B, actE, &pa2z, po);
       } else {
-        View gzsa = dx(pg, {{dzp1[0], &q[0]->layers[1], Hp}, {dzp1[1], &q[1]->layers[1], Hp}}, Z, B, ACT_NONE,
-                       nullptr);
+        View gzsa = dx(pg, {{dzp1[0], &q[0]->layers[1], Hp}, {dzp1[1], &q[1]->layers[1], Hp}}, Z, B);
         dpa2 = dx(pg, {{gzsa, &fe.layers[5], 0}}, H, B, actE, &pa2z);
       }
-      out_t = false;
-      View dpa1 = dx(pg, {{dpa2, &fe.layers[4], 0}}, H, B, actE, &pa1z);
-      out_t = true;
+      View dpa1 = dx(pg, {{dpa2, &fe.layers[4], 0}}, H, B, actE, &pa1z, po);
       // d action = sum of three paths, then tanh' (actor output)
       std::vector<DxTerm> t3{
           {dxp01[0], &q[0]->layers[0], Sp}, {dxp01[1], &q[1]->layers[0], Sp}, {dpa1, &fe.layers[3], Zp}};
@@ -3657,18 +3748,16 @@ struct Engine {
       // scheduler orders them against the pre-update weights (as autograd does)
       View ap2s = ap2.sub(0, B), ap1s = ap1.sub(0, B);
       const View ap2zs = actP == ACT_ELU ? ap2z.sub(0, B) : View{}, ap1zs = actP == ACT_ELU ? ap1z.sub(0, B) : View{};
-      View dl2 = dx(pg, {{dl3, &pi.layers[3], 0}}, H, B, actP, dsrc_of(actP, ap2s, ap2zs), nullptr, nullptr,
-                    prea ? &p3 : nullptr);
+      View dl2 = dx(pg, {{dl3, &pi.layers[3], 0}}, H, B, actP, dsrc_of(actP, ap2s, ap2zs),
+                    DxOpt().pre_gemm(prea ? &p3 : nullptr));
       dw(pg, pi.layers[3], dl3, {ap2s}, B, CNT_ADAM_PI, cfg.policy_lr);
       View dl1 = dx(pg, {{dl2, &pi.layers[2], 0}}, H, B, actP, dsrc_of(actP, ap1s, ap1zs));
       dw(pg, pi.layers[2], dl2, {ap1s}, B, CNT_ADAM_PI, cfg.policy_lr);
       const View ap0s = ap0.sub(0, B);
-      (nbd ? out_n : out_t) = false;
-      View gl0 = dx(pg, {{dl1, &pi.layers[1], 0}}, H, B, ACT_NONE, nullptr, nullptr, nbd ? &ap0s : nullptr);
-      out_n = out_t = true;
+      View gl0 = dx(pg, {{dl1, &pi.layers[1], 0}}, H, B, DxOpt().nb_defer(nbd ? &ap0s : nullptr).images(!nbd, nbd));
       dw(pg, pi.layers[1], dl1, {ap0s, fzs}, B, CNT_ADAM_PI, cfg.policy_lr);
       if (nbd) {
-        dw(pg, pi.layers[0], gl0, {s}, B, CNT_ADAM_PI, cfg.policy_lr, nullptr, nullptr, &ap0s);
+        dw(pg, pi.layers[0], gl0, {s}, B, CNT_ADAM_PI, cfg.policy_lr, DwOpt().nb_defer(&ap0s));
       } else {
         View dl0 = normbwd(pg, gl0, ap0s);
         dw(pg, pi.layers[0], dl0, {s}, B, CNT_ADAM_PI, cfg.policy_lr);
@@ -3765,11 +3854,6 @@ struct Engine {
   }
   float* qloss_part = nullptr;
   float* ploss_part = nullptr;
-  // fwd outputs get a T image (weight-gradient B operand) unless out_t is cleared around the
-  // forward-only layers (fixed and target networks, the policy pass through the critics): one
-  // store per lane and the written-back bytes of each such layer saved
-  bool out_t = true;
-  bool out_n = true;  // (the same for the N image: dx / normbwd outputs only a DW reads)
 
   // Algebraic folds of TD7's linear zsa3 layer into its consumers (build_td7): on when
   // every block is 16-aligned and zs_dim = hdim (the folded block replaces the zsa block in place).
@@ -3809,7 +3893,7 @@ struct Engine {
     for (int n = 0; n < 2; ++n) {
       const Layer& L1 = net(n ? "target_q2" : "target_q1").layers[1];
       const Layer& L3 = fet.layers[5];
-      dx(pg, {{wview_n(L1, L1.seg_p[0], H), &L3, 0}}, H, H, ACT_NONE, nullptr, &tfold_w[n]);
+      dx(pg, {{wview_n(L1, L1.seg_p[0], H), &L3, 0}}, H, H, DxOpt().out_into(&tfold_w[n]));
       Op op{};
       op.kind = OP_FOLDBIAS;
       FoldBiasArgs& f = op.fb;
@@ -3867,10 +3951,11 @@ struct Engine {
   // the first layer is recomputed in-tile by the second too, its a' segment first (two-stage prologue,
   // GemmArgs::has_pre 4, whose epilogue is the q partials: two hidden layers only): the target branch's
   // first layer costs no level of its own.  Without the fusion it is its own level, in at most 32-wide
-  // tiles (pl_src), so both give the same floats.
+  // tiles (FwdOpt::pl_src), so both give the same floats.
   // hz: the pre-activations too when the backward needs them (ELU critics; the last layer's with an N image,
   // for the loss head's rows)
-  void mlp_critic_fwd(Prog& pg, Net& Q, const View& sv, const View& av, std::vector<View>& hs,
+  // out_t: the outputs keep a T image (false: a forward-only pass, no weight gradient reads them)
+  void mlp_critic_fwd(Prog& pg, Net& Q, const View& sv, const View& av, std::vector<View>& hs, bool out_t,
                       const PreUse* pre = nullptr, bool last_t = true, bool qd = false, std::vector<View>* hz = nullptr) {
     const int D = (int)Q.layers.size() - 1;
     hs.assign(D, View{});
@@ -3885,25 +3970,22 @@ struct Engine {
     if (two) {
       hs[0] = buf(B, Q.layers[0].out, true, false);  // (layout of the consumer's A operand only: never stored)
     } else {
-      pl_src = use_pl || (pre && shape);
-      hs[0] = fwd(pg, Q.layers[0], {{sv}, {av}}, B, actC, zp(0), false, nullptr, 0, nullptr, nullptr, pre, nullptr,
-                  D == 1);
-      pl_src = false;
+      hs[0] = fwd(pg, Q.layers[0], {{sv}, {av}}, B, actC,
+                  FwdOpt().keep_pre(zp(0), D == 1).pre_gemm(pre).keep_t(out_t).pl_source(use_pl || (pre && shape)));
     }
-    const bool keep = out_t;
     for (int i = 1; i < D; ++i) {
       const bool last = i == D - 1;
-      out_t = keep && (!last || last_t);  // (last_t = false: only the head reads the last layer, in the N image)
       PreUse pl = i == 1 && (use_pl || two) ? pre_layer(Q.layers[0], {sv, av}, two ? pre->a.seg : -1) : PreUse{};
       if (i == 1 && two) {
         pl.kind = 4;
         pl.a2 = pre->a;
         pl.rd.insert(pl.rd.end(), pre->rd.begin(), pre->rd.end());
       }
-      hs[i] = fwd(pg, Q.layers[i], {{hs[i - 1]}}, B, actC, zp(i), false, nullptr, 0, nullptr, nullptr,
-                  pl.kind >= 3 ? &pl : nullptr, last && qd ? &Q.layers[D] : nullptr, last);
+      // (last_t = false: only the head reads the last layer, in the N image)
+      hs[i] = fwd(pg, Q.layers[i], {{hs[i - 1]}}, B, actC,
+                  FwdOpt().keep_pre(zp(i), last).pre_gemm(pl.kind >= 3 ? &pl : nullptr)
+                      .q_dot(last && qd ? &Q.layers[D] : nullptr).keep_t(out_t && (!last || last_t)));
     }
-    out_t = keep;
   }
   // TD3 / SAC: the critic loss head and the actor objective's head fused into the DX of each
   // critic's last hidden layer (GemmArgs::has_pre 2; one level fewer on the critic chain and on
@@ -3961,15 +4043,14 @@ struct Engine {
     const int D = (int)HS.size();
     const Layer& Lout = pi.layers[D];
     // actor on [s; s'] (target policy aliases the policy, Q1; SAC policy unchanged until its step)
-    pl_src = prelayer_ok(pi.layers[0], pi.layers[1]);
     std::vector<View> h(D), hz(D);  // (hz: an ELU actor's pre-activations, for the policy backward)
     const bool pz = actP == ACT_ELU;
-    h[0] = fwd(pg, pi.layers[0], {{ss}}, B2, actP, pz ? &hz[0] : nullptr, false);
-    pl_src = false;
-    const PreUse pl0 = prelayer_ok(pi.layers[0], pi.layers[1]) ? pre_layer(pi.layers[0], {ss}) : PreUse{};
+    const bool pl01 = prelayer_ok(pi.layers[0], pi.layers[1]);  // (the second layer recomputes the first in-tile)
+    h[0] = fwd(pg, pi.layers[0], {{ss}}, B2, actP, FwdOpt().keep_pre(pz ? &hz[0] : nullptr).pl_source(pl01));
+    const PreUse pl0 = pl01 ? pre_layer(pi.layers[0], {ss}) : PreUse{};
     for (int i = 1; i < D; ++i)
-      h[i] = fwd(pg, pi.layers[i], {{h[i - 1]}}, B2, actP, pz ? &hz[i] : nullptr, false, nullptr, 0, nullptr, nullptr,
-                 i == 1 && pl0.kind == 3 ? &pl0 : nullptr);
+      h[i] = fwd(pg, pi.layers[i], {{h[i - 1]}}, B2, actP,
+                 FwdOpt().keep_pre(pz ? &hz[i] : nullptr).pre_gemm(i == 1 && pl0.kind == 3 ? &pl0 : nullptr));
     const View hl = h[D - 1];  // the last hidden layer's output
     View actv, raw, logpi;
     // TD3: the target critics' first layer recomputes a' in-tile (pre-GEMM, as TD7)
@@ -3977,8 +4058,8 @@ struct Engine {
     const View h1n = hl.sub(B, B);
     const PreUse pn1 = prea ? pre_actor_fwd(Lout, h1n, &eps, 1) : PreUse{};
     if (!sac) {
-      actv = prea ? fwd(pg, Lout, {{hl.sub(0, B)}}, B, ACT_TANH, nullptr, false)
-                  : fwd(pg, Lout, {{hl}}, B2, ACT_TANH, nullptr, false, &eps, B);
+      actv = prea ? fwd(pg, Lout, {{hl.sub(0, B)}}, B, ACT_TANH)
+                  : fwd(pg, Lout, {{hl}}, B2, ACT_TANH, FwdOpt().noised(&eps, B));
     } else if (sac_fwd_fused()) {  // the rsample in the raw head's epilogue (one level fewer)
       actv = buf(B2, A);
       logpi = vec(B2);
@@ -3996,28 +4077,18 @@ struct Engine {
       a.eps_row_split = B;
       sfu.rd = {eps.id, eps2.id};
       sfu.wr = {actv.id, logpi.id};
-      raw = fwd(pg, Lout, {{hl}}, B2, ACT_NONE, nullptr, false, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
-                false, &sfu);
+      raw = fwd(pg, Lout, {{hl}}, B2, ACT_NONE, FwdOpt().sac_fwd(&sfu));
     } else {
-      raw = fwd(pg, Lout, {{hl}}, B2, ACT_NONE, nullptr, false);
+      raw = fwd(pg, Lout, {{hl}}, B2, ACT_NONE);
       actv = buf(B2, A);
       logpi = vec(B2);
-      Op op{};
-      op.kind = OP_SAC_ACTOR;
+      Op op = sac_actor_op(OP_SAC_ACTOR, raw.m, B2);
       SacActorArgs& a = op.sac;
-      a.out = raw.m;
-      a.A = A;
-      a.rows = B2;
       a.eps = eps.m;
       a.eps2 = eps2.m;
       a.eps_row_split = B;
       a.act = actv.m;
       a.logpi = logpi.p;
-      a.min_log_std = cfg.min_log_std;
-      a.max_log_std = cfg.max_log_std;
-      a.mean_off = 0;
-      a.ls_off = A;
-      op.wg_count = cdiv(B2, kThreads);
       pg.add(op, {raw.id, eps.id, eps2.id}, {actv.id, logpi.id});
     }
     View a_pi = actv.sub(0, B), a_next = prea ? a_pi : actv.sub(B, B);  // (pre: layout only)
@@ -4026,13 +4097,12 @@ struct Engine {
     const PreUse* tpre = prea ? &pn1 : (psac.kind == 5 ? &psac : nullptr);
     // target critics + y
     std::vector<View> th[2];
-    out_t = false;  // (forward only)
     const bool hdx = mlp_headdx();
-    for (int n = 0; n < 2; ++n) mlp_critic_fwd(pg, *tq[n], s2, a_next, th[n], tpre, true, hdx);
-    out_t = true;
+    for (int n = 0; n < 2; ++n)  // (forward only)
+      mlp_critic_fwd(pg, *tq[n], s2, a_next, th[n], /*out_t*/ false, tpre, true, hdx);
     // online critics
     std::vector<View> c[2], cz[2];
-    for (int n = 0; n < 2; ++n) mlp_critic_fwd(pg, *q[n], s, act_in, c[n], nullptr, true, hdx, &cz[n]);
+    for (int n = 0; n < 2; ++n) mlp_critic_fwd(pg, *q[n], s, act_in, c[n], /*out_t*/ true, nullptr, true, hdx, &cz[n]);
     // (the loss heads' derivative rows: ELU' reads the pre-activation; ReLU' / identity the output)
     const bool cze = actC == ACT_ELU;
     // (the last hidden layers and the heads' layers)
@@ -4087,7 +4157,7 @@ struct Engine {
           if (n == 0) hu.wr.insert(hu.wr.end(), {prio.id, qloss_id});
           // (the head forms dZ = dq w act'(segment 0): an ELU critic's pre-activations, a ReLU critic's outputs)
           d0f[n] = dx(pg, {{cze ? cz[n][D - 1] : c1[n], &q[n]->layers[D - 1], 0}}, HS[D - 2], B, actC,
-                      dsrc_of(actC, c[n][D - 2], cz[n][D - 2]), nullptr, nullptr, nullptr, &hu);
+                      dsrc_of(actC, c[n][D - 2], cz[n][D - 2]), DxOpt().head_use(&hu));
         }
       }
     }
@@ -4110,9 +4180,11 @@ struct Engine {
     int ngsq = 0;
     if (policy) {
       std::vector<View> pc[2], pcz[2];
-      for (int n = 0; n < 2; ++n) mlp_critic_fwd(pg, *q[n], s, a_pi, pc[n], nullptr, false, hdx, &pcz[n]);
+      for (int n = 0; n < 2; ++n)
+        mlp_critic_fwd(pg, *q[n], s, a_pi, pc[n], /*out_t*/ true, nullptr, /*last_t*/ false, hdx, &pcz[n]);
       const View p1[2] = {pc[0][D - 1], pc[1][D - 1]};
       // (no weight gradient of the critics in the policy pass: the gradients keep N images only)
+      const DxOpt po = DxOpt().no_t();
       View dzp1[2];
       if (!hdx) dzp1[0] = buf(B, H, true, false), dzp1[1] = buf(B, H, true, false);
       ploss_part = mem.make<float>((size_t)hw * 4);
@@ -4134,14 +4206,12 @@ struct Engine {
         }
         set_head_parts(h, p1, nullptr, rd);
         ploss_id = next_id++;
-        out_t = false;
         for (int n = 0; n < 2; ++n) {
           HeadUse hu{h, n, rd, {}};
           if (n == 0) hu.wr.push_back(ploss_id);
           dzp0[n] = dx(pg, {{cze ? pcz[n][D - 1] : p1[n], &q[n]->layers[D - 1], 0}}, HS[D - 2], B, actC,
-                       dsrc_of(actC, pc[n][D - 2], pcz[n][D - 2]), nullptr, nullptr, nullptr, &hu);
+                       dsrc_of(actC, pc[n][D - 2], pcz[n][D - 2]), DxOpt(po).head_use(&hu));
         }
-        out_t = true;
       } else {
         Op op = head_op(HEAD_MLP_POLICY, Bv);
         HeadArgs& h = op.head;
@@ -4163,11 +4233,9 @@ struct Engine {
           rd.push_back(R_LA);
         }
         pg.add(op, rd, {dzp1[0].id, dzp1[1].id, ploss_id = next_id++});
-        out_t = false;
         for (int n = 0; n < 2; ++n)
           dzp0[n] = dx(pg, {{dzp1[n], &q[n]->layers[D - 1], 0}}, HS[D - 2], B, actC,
-                       dsrc_of(actC, pc[n][D - 2], pcz[n][D - 2]));
-        out_t = true;
+                       dsrc_of(actC, pc[n][D - 2], pcz[n][D - 2]), po);
       }
       // ---- offline (rle_config_ext bc_alpha): L = -lmbda mean(min Q) + mse(pi(s), a), lmbda = bc_alpha /
       // mean|min Q| (detached).  Scale at the end: the chain above and below stays the online one (dL/dq = -1/B),
@@ -4230,11 +4298,10 @@ struct Engine {
         }
       }
       // (deeper critics: on down to the first hidden layer; no weight gradient reads these)
-      out_t = false;
       for (int i = D - 2; i >= 1; --i)
         for (int n = 0; n < 2; ++n)
-          dzp0[n] = dx(pg, {{dzp0[n], &q[n]->layers[i], 0}}, HS[i - 1], B, actC, dsrc_of(actC, pc[n][i - 1], pcz[n][i - 1]));
-      out_t = true;
+          dzp0[n] = dx(pg, {{dzp0[n], &q[n]->layers[i], 0}}, HS[i - 1], B, actC,
+                       dsrc_of(actC, pc[n][i - 1], pcz[n][i - 1]), po);
       View dout;
       PreUse pdout{};  // TD3: d1 recomputes dout in-tile
       if (!sac) {
@@ -4261,30 +4328,19 @@ struct Engine {
           a.ls_off = A;
           sbu.rd = {raw.id, eps2.id, R_LA};
           sbu.wr = {dout.id};
-          dx(pg, {{dzp0[0], &q[0]->layers[0], Sp}, {dzp0[1], &q[1]->layers[0], Sp}}, A, B, ACT_NONE, nullptr,
-             nullptr, nullptr, nullptr, nullptr, &sbu);
+          dx(pg, {{dzp0[0], &q[0]->layers[0], Sp}, {dzp0[1], &q[1]->layers[0], Sp}}, A, B, DxOpt().sac_bwd(&sbu));
         }
       }
       if (sac && !sac_bwd_fused()) {
-        View da = dx(pg, {{dzp0[0], &q[0]->layers[0], Sp}, {dzp0[1], &q[1]->layers[0], Sp}}, A, B, ACT_NONE,
-                     nullptr);
-        Op op{};
-        op.kind = OP_SAC_ACTOR_BWD;
+        View da = dx(pg, {{dzp0[0], &q[0]->layers[0], Sp}, {dzp0[1], &q[1]->layers[0], Sp}}, A, B);
+        Op op = sac_actor_op(OP_SAC_ACTOR_BWD, raw.m, Bv);  // (rows of the padded batch past Bv keep a zero gradient)
         SacActorArgs& a = op.sac;
-        a.out = raw.m;
-        a.A = A;
-        a.rows = Bv;  // (rows of the padded batch past it keep a zero gradient)
         a.eps2 = eps2.m;
-        a.min_log_std = cfg.min_log_std;
-        a.max_log_std = cfg.max_log_std;
-        a.mean_off = 0;
-        a.ls_off = A;
         a.da = da.m;
         a.dout = dout.m;
         a.log_alpha = alpha_src();
         a.alpha_lin = cfg.tmp >= 0.f;
         a.inv_b = 1.f / (float)Bv;
-        op.wg_count = cdiv(Bv, kThreads);
         pg.add(op, {raw.id, eps2.id, da.id, R_LA}, {dout.id});
       }
       if (!sac) {
@@ -4317,24 +4373,22 @@ struct Engine {
       adam_gscale = offline3() ? bc_s + 1 : nullptr;
       // SAC: d1 (the gradient through the raw head, K = 2A <= 48) recomputed in-tile by d0's DX
       const bool pld = sac && sac_bwd_fused() && prelayer_ok_dx(Lout, pi.layers[D - 1]);
-      pl_src = pld;
-      View d = dx(pg, {{dout, &Lout, 0}}, HS[D - 1], B, actP, dsrc_of(actP, hsub[D - 1], hzsub[D - 1]), nullptr, nullptr,
-                  prea ? &pdout : nullptr);
-      pl_src = false;
+      View d = dx(pg, {{dout, &Lout, 0}}, HS[D - 1], B, actP, dsrc_of(actP, hsub[D - 1], hzsub[D - 1]),
+                  DxOpt().pre_gemm(prea ? &pdout : nullptr).pl_source(pld));
       // (d0 reads the raw head's pre-update weights when it recomputes d1: emitted before that Adam)
       const PreUse pd1 = pld ? pre_layer_dx(Lout, dout, hsub[D - 1]) : PreUse{};
       View dp;
-      if (pld) dp = dx(pg, {{d, &pi.layers[D - 1], 0}}, HS[D - 2], B, actP, &hsub[D - 2], nullptr, nullptr, &pd1);
-      dw(pg, Lout, dout, {hsub[D - 1]}, B, CNT_ADAM_PI, cfg.policy_lr, gl[D].first, gl[D].second);
+      if (pld) dp = dx(pg, {{d, &pi.layers[D - 1], 0}}, HS[D - 2], B, actP, &hsub[D - 2], DxOpt().pre_gemm(&pd1));
+      dw(pg, Lout, dout, {hsub[D - 1]}, B, CNT_ADAM_PI, cfg.policy_lr, DwOpt().gsq_parts(gl[D]));
       if (!pld) dp = dx(pg, {{d, &pi.layers[D - 1], 0}}, HS[D - 2], B, actP, dsrc_of(actP, hsub[D - 2], hzsub[D - 2]));
-      dw(pg, pi.layers[D - 1], d, {hsub[D - 2]}, B, CNT_ADAM_PI, cfg.policy_lr, gl[D - 1].first, gl[D - 1].second);
+      dw(pg, pi.layers[D - 1], d, {hsub[D - 2]}, B, CNT_ADAM_PI, cfg.policy_lr, DwOpt().gsq_parts(gl[D - 1]));
       d = dp;
       for (int i = D - 2; i >= 1; --i) {  // (deeper actors)
         dp = dx(pg, {{d, &pi.layers[i], 0}}, HS[i - 1], B, actP, dsrc_of(actP, hsub[i - 1], hzsub[i - 1]));
-        dw(pg, pi.layers[i], d, {hsub[i - 1]}, B, CNT_ADAM_PI, cfg.policy_lr, gl[i].first, gl[i].second);
+        dw(pg, pi.layers[i], d, {hsub[i - 1]}, B, CNT_ADAM_PI, cfg.policy_lr, DwOpt().gsq_parts(gl[i]));
         d = dp;
       }
-      dw(pg, pi.layers[0], d, {s}, B, CNT_ADAM_PI, cfg.policy_lr, gl[0].first, gl[0].second);
+      dw(pg, pi.layers[0], d, {s}, B, CNT_ADAM_PI, cfg.policy_lr, DwOpt().gsq_parts(gl[0]));
       adam_ptau = 0.f;
       adam_gscale = nullptr;
       if (gsq) {
@@ -4653,50 +4707,28 @@ struct Engine {
     const bool sac = algo == RLE_SAC;
     alloc_folds();
     multi_k = pair_k();
+    // K steps from batch set `set` on, as one program.  TD7 / TD3: policy, plain, ...; SAC: every step is a policy step
+    auto steps = [&](int set, int K, bool first_policy) {
+      Prog p = plan_build([&](Prog& pg) {
+        for (int j = 0; j < K; ++j) {
+          const bool policy = sac || (j % 2 == 0) == first_policy;
+          if (algo == RLE_TD7) build_td7(pg, policy, (set + j) % 2);
+          else build_mlp(pg, policy, (set + j) % 2);
+        }
+      });
+      return capture(p);
+    };
     for (int set = 0; set < 2; ++set) {
       Prog pp;
       pp.xcd = plan.xcd;
       build_prime(pp, sac, set);
       g_prime[set] = capture(pp);
-      if (algo == RLE_TD7) {
-        Prog p1 = plan_build([&](Prog& p) { build_td7(p, true, set); });
-        g_pol[set] = capture(p1);
-        Prog p2 = plan_build([&](Prog& p) { build_td7(p, false, set); });
-        g_pln[set] = capture(p2);
-        if (multi_k) {
-          Prog p3 = plan_build([&](Prog& p) {
-            for (int j = 0; j < multi_k; ++j) build_td7(p, j % 2 == 0, (set + j) % 2);
-          });
-          g_pair[set] = capture(p3);
-          for (int r = 0; r < 2; ++r) {
-            if (kRemK[r] >= multi_k) continue;
-            Prog p4 = plan_build([&](Prog& p) {
-              for (int j = 0; j < kRemK[r]; ++j) build_td7(p, j % 2 == 0, (set + j) % 2);
-            });
-            g_rem[r][set] = capture(p4);
-          }
-        }
-      } else {
-        Prog p1 = plan_build([&](Prog& p) { build_mlp(p, true, set); });
-        g_pol[set] = capture(p1);
-        if (!sac) {
-          Prog p2 = plan_build([&](Prog& p) { build_mlp(p, false, set); });
-          g_pln[set] = capture(p2);
-        }
-        if (multi_k) {  // TD3: policy, plain, ...; SAC: every step is a policy step
-          Prog p3 = plan_build([&](Prog& p) {
-            for (int j = 0; j < multi_k; ++j) build_mlp(p, sac || j % 2 == 0, (set + j) % 2);
-          });
-          g_pair[set] = capture(p3);
-          for (int r = 0; r < 2; ++r) {
-            if (kRemK[r] >= multi_k) continue;
-            Prog p4 = plan_build([&](Prog& p) {
-              for (int j = 0; j < kRemK[r]; ++j) build_mlp(p, sac || j % 2 == 0, (set + j) % 2);
-            });
-            g_rem[r][set] = capture(p4);
-          }
-        }
-      }
+      g_pol[set] = steps(set, 1, true);
+      if (!sac) g_pln[set] = steps(set, 1, false);
+      if (!multi_k) continue;
+      g_pair[set] = steps(set, multi_k, true);
+      for (int r = 0; r < 2; ++r)
+        if (kRemK[r] < multi_k) g_rem[r][set] = steps(set, kRemK[r], true);
     }
     if (algo == RLE_TD7) {
       Prog ph;
@@ -5903,23 +5935,10 @@ int rle_act(rle_engine* h, const float* obs, int n, float* out) {
     HIPCHK(hipSetDevice(e.cfg.device));
     auto it = e.act_graphs.find(n);
     if (it == e.act_graphs.end()) {
-      rle::Prog pg;
+      rle::Prog pg = e.aux_prog();
       const int M = rle::r16(n);  // image rows; rows n..M-1 are padding
       rle::View in = e.buf(M, e.S, true, false);
-      rle::View o;
-      if (e.algo == RLE_TD7) {  // td7.py:158-162
-        rle::Net& fe = e.net("fixed_encoder");
-        rle::Net& pi = e.net("policy");
-        rle::View h1 = e.fwd(pg, fe.layers[0], {{in}}, M, e.actE, nullptr, false);
-        rle::View h2 = e.fwd(pg, fe.layers[1], {{h1}}, M, e.actE, nullptr, false);
-        rle::View zs = e.fwd(pg, fe.layers[2], {{h2}}, M, rle::ACT_NONE, nullptr, true);
-        rle::View p0 = e.fwd(pg, pi.layers[0], {{in}}, M, rle::ACT_NONE, nullptr, true);
-        rle::View p1 = e.fwd(pg, pi.layers[1], {{p0}, {zs}}, M, e.actP, nullptr, false);
-        rle::View p2 = e.fwd(pg, pi.layers[2], {{p1}}, M, e.actP, nullptr, false);
-        o = e.fwd(pg, pi.layers[3], {{p2}}, M, rle::ACT_TANH, nullptr, false);
-      } else {
-        o = e.mlp_fwd(pg, e.net("policy"), {{in}}, M, rle::ACT_NONE, e.actP);
-      }
+      rle::View o = e.policy_fwd(pg, in, M, rle::ACT_NONE);
       rle::Graph G = e.capture(pg);
       it = e.act_graphs.emplace(n, std::make_pair(G, o)).first;
       e.act_inputs[n] = in;
@@ -5972,53 +5991,19 @@ int rle_act_sample(rle_engine* h, const float* obs, int n, int mode, const float
       as.ctl = (int*)e.pin.alloc(64);
       as.eps = (float*)e.pin.alloc((size_t)n * e.A * 4);
       as.out = (float*)e.pin.alloc((size_t)n * e.A * 4);
-      rle::ActArgs ao{};
-      HIPCHK(hipHostGetDevicePointer((void**)&ao.out, as.out, 0));
-      HIPCHK(hipHostGetDevicePointer((void**)&ao.ctl, as.ctl, 0));
-      HIPCHK(hipHostGetDevicePointer((void**)&ao.eps, as.eps, 0));
-      ao.scale = e.act_map;
-      ao.bias = e.act_map + e.A;
-      ao.sigma = e.act_map + 2 * e.A;
-      ao.n = n;
-      ao.A = e.A;
-      ao.seed = e.cfg.seed * 0x9E3779B97F4A7C15ull + 0x5851F42D4C957F2Dull;  // own stream, not the step's
-      rle::Prog pg;
-      rle::View in = as.in;
-      auto tanh_act = [&](rle::Prog& p) {  // the last GEMM becomes the act epilogue (EPI_ACT)
-        rle::Op& op = p.items.back().ops[0];
+      const rle::ActArgs ao = e.act_args(as, n);
+      rle::Prog pg = e.aux_prog();
+      const bool sac = e.algo == RLE_SAC;
+      const rle::View head = e.policy_fwd(pg, as.in, M, sac ? rle::ACT_NONE : rle::ACT_TANH);
+      if (!sac) {  // td7.py:141-162, td3.py:114-135: the tanh head's GEMM becomes the act epilogue (EPI_ACT)
+        rle::Op& op = pg.items.back().ops[0];
         op.gemm.epi = rle::EPI_ACT;
         op.gemm.ao = ao;
         rle::gemm_finalize(op.gemm);
-      };
-      if (e.algo == RLE_TD7) {  // td7.py:141-162
-        rle::Net& fe = e.net("fixed_encoder");
-        rle::Net& pi = e.net("policy");
-        rle::View h1 = e.fwd(pg, fe.layers[0], {{in}}, M, e.actE, nullptr, false);
-        rle::View h2 = e.fwd(pg, fe.layers[1], {{h1}}, M, e.actE, nullptr, false);
-        rle::View zs = e.fwd(pg, fe.layers[2], {{h2}}, M, rle::ACT_NONE, nullptr, true);
-        rle::View p0 = e.fwd(pg, pi.layers[0], {{in}}, M, rle::ACT_NONE, nullptr, true);
-        rle::View p1 = e.fwd(pg, pi.layers[1], {{p0}, {zs}}, M, e.actP, nullptr, false);
-        rle::View p2 = e.fwd(pg, pi.layers[2], {{p1}}, M, e.actP, nullptr, false);
-        e.fwd(pg, pi.layers[3], {{p2}}, M, rle::ACT_TANH, nullptr, false);
-        tanh_act(pg);
-      } else if (e.algo == RLE_TD3) {  // td3.py:114-135
-        e.mlp_fwd(pg, e.net("policy"), {{in}}, M, rle::ACT_TANH, e.actP);
-        tanh_act(pg);
       } else {  // sac.py:132-159
-        rle::View raw = e.mlp_fwd(pg, e.net("policy"), {{in}}, M, rle::ACT_NONE, e.actP);
-        rle::Op op{};
-        op.kind = rle::OP_SAC_ACTOR;
-        rle::SacActorArgs& sa = op.sac;
-        sa.ao = ao;
-        sa.out = raw.m;
-        sa.A = e.A;
-        sa.rows = n;
-        sa.min_log_std = e.cfg.min_log_std;
-        sa.max_log_std = e.cfg.max_log_std;
-        sa.mean_off = 0;
-        sa.ls_off = e.A;
-        op.wg_count = rle::cdiv(n, rle::kThreads);
-        pg.add(op, {raw.id}, {});
+        rle::Op op = e.sac_actor_op(rle::OP_SAC_ACTOR, head.m, n);
+        op.sac.ao = ao;
+        pg.add(op, {head.id}, {});
       }
       as.G = e.capture(pg);
       it = e.act_samplers.emplace(n, as).first;
@@ -6027,17 +6012,7 @@ int rle_act_sample(rle_engine* h, const float* obs, int n, int mode, const float
     if (n == 1 && !e.chain_tried) {
       e.chain_tried = true;
       static const bool no_chain = std::getenv("RLE_NO_ACT_CHAIN") != nullptr;  // A/B
-      rle::ActArgs ao{};
-      HIPCHK(hipHostGetDevicePointer((void**)&ao.out, as.out, 0));
-      HIPCHK(hipHostGetDevicePointer((void**)&ao.ctl, as.ctl, 0));
-      HIPCHK(hipHostGetDevicePointer((void**)&ao.eps, as.eps, 0));
-      ao.scale = e.act_map;
-      ao.bias = e.act_map + e.A;
-      ao.sigma = e.act_map + 2 * e.A;
-      ao.n = 1;
-      ao.A = e.A;
-      ao.seed = e.cfg.seed * 0x9E3779B97F4A7C15ull + 0x5851F42D4C957F2Dull;
-      e.chain_ok = !no_chain && e.build_chain(ao);
+      e.chain_ok = !no_chain && e.build_chain(e.act_args(as, 1));
     }
     if (n == 1 && e.chain_ok) {  // one launch, in-kernel hand-offs (kernels.hip rle_act_chain)
       rle::ActChainArgs& c = e.chain;
@@ -6354,7 +6329,7 @@ int rle_eval(rle_engine* h, int what, const char* net, const char* enc, const fl
     auto it = e.eval_graphs.find(key);
     if (it == e.eval_graphs.end()) {
       rle::Net& N = e.net(net);
-      rle::Prog pg;
+      rle::Prog pg = e.aux_prog();
       const int M = rle::r16(n);
       Engine::EvalGraph eg;
       eg.in0 = e.buf(M, e.S, true, false);
@@ -6365,10 +6340,10 @@ int rle_eval(rle_engine* h, int what, const char* net, const char* enc, const fl
           REQUIRE(N.kind == "sale_critic" && E.kind == "sale_enc", "eval: Q needs a critic net and an encoder");
           rle::View zs = e.enc_zs(pg, E, eg.in0, M);
           rle::View zsa = e.enc_zsa(pg, E, zs, eg.in1, M);
-          rle::View c01 = e.fwd(pg, N.layers[0], {{eg.in0}, {eg.in1}}, M, rle::ACT_NONE, nullptr, true);
-          rle::View c1 = e.fwd(pg, N.layers[1], {{c01}, {zsa}, {zs}}, M, e.actC, nullptr, false);
-          rle::View c2 = e.fwd(pg, N.layers[2], {{c1}}, M, e.actC, nullptr, false);
-          eg.out = e.fwd(pg, N.layers[3], {{c2}}, M, rle::ACT_NONE, nullptr, false);
+          rle::View c01 = e.fwd(pg, N.layers[0], {{eg.in0}, {eg.in1}}, M, rle::ACT_NONE, Engine::FwdOpt().norm());
+          rle::View c1 = e.fwd(pg, N.layers[1], {{c01}, {zsa}, {zs}}, M, e.actC);
+          rle::View c2 = e.fwd(pg, N.layers[2], {{c1}}, M, e.actC);
+          eg.out = e.fwd(pg, N.layers[3], {{c2}}, M, rle::ACT_NONE);
         } else {  // MLPCritic.estimate_q_value (mlp.py:98-101)
           REQUIRE(N.kind == "mlp_critic", "eval: Q needs a critic net");
           eg.out = e.mlp_fwd(pg, N, {{eg.in0}, {eg.in1}}, M, rle::ACT_NONE, e.actC);
@@ -6402,7 +6377,7 @@ int rle_sac_rsample(rle_engine* h, const float* mean, const float* log_std, cons
     const std::string key = "rsample|" + std::to_string(n);
     auto it = e.eval_graphs.find(key);
     if (it == e.eval_graphs.end()) {
-      rle::Prog pg;
+      rle::Prog pg = e.aux_prog();
       const int M = rle::r16(n);
       Engine::EvalGraph eg;
       eg.in0 = e.buf(M, 2 * A);              // raw head output: mean | log_std (as mlp.4's output)
@@ -6410,22 +6385,13 @@ int rle_sac_rsample(rle_engine* h, const float* mean, const float* log_std, cons
       eg.out = e.buf(M, A);                  // tanh action
       rle::View lp = e.vec(M);
       eg.out_vec = lp.p;
-      rle::Op op{};
-      op.kind = rle::OP_SAC_ACTOR;
+      rle::Op op = e.sac_actor_op(rle::OP_SAC_ACTOR, eg.in0.m, n);
       rle::SacActorArgs& sa = op.sac;
-      sa.out = eg.in0.m;
-      sa.A = A;
-      sa.rows = n;
       sa.eps = eg.in1.m;
       sa.eps2 = eg.in1.m;
       sa.eps_row_split = 0;  // every row draws from eps
       sa.act = eg.out.m;
       sa.logpi = lp.p;
-      sa.min_log_std = e.cfg.min_log_std;
-      sa.max_log_std = e.cfg.max_log_std;
-      sa.mean_off = 0;
-      sa.ls_off = A;
-      op.wg_count = rle::cdiv(n, rle::kThreads);
       pg.add(op, {eg.in0.id, eg.in1.id}, {eg.out.id, lp.id});
       eg.width = A;
       eg.G = e.capture(pg);

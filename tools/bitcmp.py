@@ -2,9 +2,20 @@
 
     RLE_LIB=lib_a.so python tools/bitcmp.py dump NAME STEPS out_a.npz
     RLE_LIB=lib_b.so python tools/bitcmp.py dump NAME STEPS out_b.npz
-    python tools/bitcmp.py cmp out_a.npz out_b.npz
+    python tools/bitcmp.py cmp out_a.npz out_b.npz [out_a_again.npz]
 
-Per step: every parameter, the priorities and the info row after a single-step replay.
+NAME: a golden of tests/golden, or edge:<case> for a case of tests/edge_cases.py (built under edge_env,
+as tests/test_shape_edges_gpu.py builds it).  Per step: every parameter, the priorities and the info row
+after a single-step replay.  The dump also holds the programs' descriptions (rle_graph_describe 0, 1, 3
+and the hard-update program; empty where the engine has none) -- with RLE_DESC_WG=1 in the environment
+they carry every op's workgroup count, so a changed tile plan shows even where the floats agree.
+
+Environment (dump): BITCMP_BURST steps per rle_step call (6: the multi-step and remainder programs);
+BITCMP_NETS nets to dump; BITCMP_FUSE_OFF the plan's fuse_off, names of rl._engine.FUSE joined by "+" or
+"all" (every fusion that is on by default); BITCMP_WIDE the plan's wide.
+
+cmp exits 1 when any array or description differs.  With a third dump (a second run of the first build),
+arrays that differ between the first build's own two runs are reported and left out of the verdict.
 """
 import os
 import sys
@@ -14,56 +25,107 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "sac-td3-td7_amd"), os.path.join(REPO, "tests")]
 
+OPT_IN = ("priosample",)  # include/rle.h RLE_FUSE_OPT_IN: off unless asked for, so not part of "all"
+DESCRIBE = {"desc_policy": 0, "desc_plain": 1, "desc_multi": 3, "desc_hard": 2}
 
-def dump(name, steps, out):
-    from conftest import load_golden
-    from harness import engine_from_golden, parse, shape_of
+
+def plan_from_env():
+    from rl import _engine as E
+
+    off, wide = os.environ.get("BITCMP_FUSE_OFF"), os.environ.get("BITCMP_WIDE")
+    if not off and not wide:
+        return None
+    names = [n for n in E.FUSE if n not in OPT_IN] if off == "all" else [n for n in (off or "").split("+") if n]
+    return E.make_plan(fuse_off=names, **({"wide": int(wide)} if wide else {}))
+
+
+def build(name, plan):
+    """(golden, engine, replay, state dim, action dim) of a golden's name or of edge:<case>."""
+    from harness import engine_from_golden
     from oracle import spec
 
-    g = load_golden(name)
+    if not name.startswith("edge:"):
+        from conftest import load_golden
+
+        g = load_golden(name)
+        return (g,) + engine_from_golden(g, plan=plan)[:2] + spec.TASKS[str(g["meta_env"])][:2]
+    import edge_cases
+
+    c = edge_cases.CASES[name[5:]]
+    g = edge_cases.golden(name[5:])
+    with edge_cases.edge_env(name[5:]):
+        if c.bc_lambda:
+            from test_offline_gpu import offline_engine
+
+            return (g,) + offline_engine(g, c.bc_lambda, plan) + (c.S, c.A)
+        return (g,) + engine_from_golden(g, plan=plan)[:2] + (c.S, c.A)
+
+
+def dump(name, steps, out):
+    from harness import parse, shape_of
+    from oracle import spec
+
+    g, eng, rep, S, A = build(name, plan_from_env())
     alg, env, H, B, Ncap, n_fill, n_steps, use_lap, seed, extra = parse(g)
     steps = min(steps, n_steps)  # (the golden's tapes cover n_steps)
-    S, A, hi = spec.TASKS[env]
-    eng, rep, tp = engine_from_golden(g)
+    tp = {k[5:]: v for k, v in g.items() if k.startswith("tape_")}
     shapes = {net: {k: np.shape(v) for k, v in p.items()}
               for net, p in spec.agent_params(alg, S, A, H, seed, **shape_of(g)).items()}
-    names = {net: list(p.keys()) for net, p in shapes.items()}
     keep = os.environ.get("BITCMP_NETS")  # comma-separated nets to dump (default: all)
     if keep:
-        names = {n: v for n, v in names.items() if n in keep.split(",")}
-    eng.set_tapes(u=tp["u"][:steps], eps=tp["eps"][:steps],
-                  eps_pi=tp.get("eps_pi", None) if "eps_pi" in tp else None)
-    res = {}
+        shapes = {n: v for n, v in shapes.items() if n in keep.split(",")}
+    res = {k: np.array(eng.describe(which)) for k, which in DESCRIBE.items()}
+    eng.set_tapes(u=tp["u"][:steps], eps=tp["eps"][:steps], eps_pi=tp.get("eps_pi"))
     burst = int(os.environ.get("BITCMP_BURST", "1"))  # steps per rle_step call (6: TD7's multi-step graphs)
     for t in range(0, steps, burst):
         res[f"info_{t}"] = np.asarray(eng.step(min(burst, steps - t)))
         if use_lap:
             res[f"prio_{t}"] = rep.get_priority(Ncap)
-        for net, ps in names.items():
-            for p in ps:
-                res[f"{t}/{net}/{p}"] = np.asarray(eng.get_param(net, p)).reshape(shapes[net][p])
+        for net, ps in shapes.items():
+            for p, shape in ps.items():
+                res[f"{t}/{net}/{p}"] = np.asarray(eng.get_param(net, p)).reshape(shape)
     np.savez(out, **res)
 
 
-def cmp(a, b):
-    A, B = np.load(a), np.load(b)
+def differing(A, B, report):
+    """Keys of A whose arrays are not bit-for-bit those of B (NaN payloads included: the info row's NaN
+    on plain steps is equal to itself)."""
+    bad = []
     for k in A.files:
         x, y = A[k], B[k]
-        d = np.abs(x.astype(np.float64) - y.astype(np.float64))
-        # bitwise (NaN payloads included: the info row's NaN on plain steps is equal to itself)
+        if x.dtype.kind == "U":  # a program description
+            if str(x) != str(y):
+                bad.append(k)
+                report(f"{k:50s} differ (program description)")
+            continue
         xb = x.view(np.uint32) if x.dtype == np.float32 else x
         yb = y.view(np.uint32) if y.dtype == np.float32 else y
-        n = int((xb != yb).sum())
+        n = int((xb != yb).sum()) if x.shape == y.shape else x.size
         if n:
-            print(f"{k:50s} differ {n:7d}/{x.size:7d} max {d.max():.3e}")
-            if x.ndim == 2:
+            bad.append(k)
+            d = np.abs(x.astype(np.float64) - y.astype(np.float64)) if x.shape == y.shape else np.array([np.inf])
+            report(f"{k:50s} differ {n:7d}/{x.size:7d} max {d.max():.3e}")
+            if x.ndim == 2 and x.shape == y.shape:
                 r, c = np.nonzero(xb != yb)
-                print(f"    rows {sorted(set((r // 16).tolist()))} (16-blocks), cols {sorted(set((c // 16).tolist()))} (16-blocks)")
-    print("compared", len(A.files), "arrays")
+                report(f"    rows {sorted(set((r // 16).tolist()))} (16-blocks), cols {sorted(set((c // 16).tolist()))} (16-blocks)")
+    return bad
+
+
+def cmp(a, b, again=None):
+    A, B = np.load(a), np.load(b)
+    unstable = []
+    if again:
+        unstable = differing(A, np.load(again), lambda line: print("unstable (first build, run to run):", line))
+    missing = sorted(set(A.files) ^ set(B.files))
+    if missing:
+        print("arrays in one dump only:", missing)
+    bad = [k for k in differing(A, B, print) if k not in unstable] if not missing else missing
+    print("compared", len(A.files), "arrays:", len(bad), "differ", f"({len(unstable)} unstable, left out)" if again else "")
+    return 1 if bad else 0
 
 
 if __name__ == "__main__":
     if sys.argv[1] == "dump":
         dump(sys.argv[2], int(sys.argv[3]), sys.argv[4])
     else:
-        cmp(sys.argv[2], sys.argv[3])
+        sys.exit(cmp(*sys.argv[2:5]))
