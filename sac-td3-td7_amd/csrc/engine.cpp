@@ -2317,6 +2317,15 @@ struct Engine {
     const float* p;
     int xs, res;
   };
+  // A layer's whole weight matrix as a forward GEMM's B operand (N image)
+  Seg wseg_n(const Layer& L) const {
+    Seg w{};
+    w.p = P + L.wn_off;
+    w.xs = L.cb;
+    w.x1 = L.out;
+    w.r1 = L.K;
+    return w;
+  }
   WSeg wblock(const Layer& L, int col0) const {
     return {P + L.wn_off + (size_t)(col0 / 16) * 256, L.cb, L.res};
   }
@@ -2338,6 +2347,21 @@ struct Engine {
     int col0;
     const View* wv = nullptr;  // ... or of a derived [out][in] matrix (T image) when L is null
   };
+  // W[:, col0 : col0 + ncols] of an input-gradient term through the T image, its rows at reduction offset roff
+  Seg wseg_t(const DxTerm& tm, int ncols, int roff) const {
+    Seg b{};
+    if (tm.L) {
+      b.p = P + tm.L->wt_off + (size_t)(tm.col0 / 16) * tm.L->rb * 256;
+      b.xs = tm.L->rb;
+    } else {
+      b.p = tm.wv->m.t + (size_t)(tm.col0 / 16) * tm.wv->m.rbs * 256;
+      b.xs = tm.wv->m.rbs;
+    }
+    b.x1 = ncols;
+    b.r0 = roff;
+    b.r1 = roff + (tm.L ? tm.L->out : tm.wv->rows);
+    return b;
+  }
 
   // A pre-GEMM (PreArgs) and the resources it reads, for fwd() / dx(): the consumer's A segment
   // a.seg is computed in-tile, so the view passed for that segment only gives its layout.
@@ -2372,12 +2396,7 @@ struct Engine {
     p.mode = GEMM_FWD;
     p.A.seg[0] = seg_n(x, 0, L.K);
     p.A.nseg = 1;
-    Seg w{};
-    w.p = P + L.wn_off;
-    w.xs = L.cb;
-    w.x1 = L.out;
-    w.r1 = L.K;
-    p.B.seg[0] = w;
+    p.B.seg[0] = wseg_n(L);
     p.B.nseg = 1;
     p.N = L.out;
     p.R = L.K;
@@ -2405,12 +2424,7 @@ struct Engine {
     p.mode = GEMM_FWD;
     p.A.seg[0] = seg_n(x, 0, L.K);
     p.A.nseg = 1;
-    Seg w{};
-    w.p = P + L.wn_off;
-    w.xs = L.cb;
-    w.x1 = L.out;
-    w.r1 = L.K;
-    p.B.seg[0] = w;
+    p.B.seg[0] = wseg_n(L);
     p.B.nseg = 1;
     p.N = L.out;
     p.R = L.K;
@@ -2467,12 +2481,7 @@ struct Engine {
       if ((int)q != lds_seg) u.rd.push_back(xs[q].id);
     }
     p.A.nseg = (int)xs.size();
-    Seg w{};
-    w.p = P + L0.wn_off;
-    w.xs = L0.cb;
-    w.x1 = L0.out;
-    w.r1 = L0.K;
-    p.B.seg[0] = w;
+    p.B.seg[0] = wseg_n(L0);
     p.B.nseg = 1;
     p.N = L0.out;
     p.R = L0.K;
@@ -2521,18 +2530,7 @@ struct Engine {
       REQUIRE(tm.dz.m.n && tm.col0 % 16 == 0 && (tm.L || (tm.wv && tm.wv->m.t)), "pre: dx term layout");
       const int wout = tm.L ? tm.L->out : tm.wv->rows;
       p.A.seg[t] = seg_n(tm.dz, roff, roff + wout);
-      Seg b{};
-      if (tm.L) {
-        b.p = P + tm.L->wt_off + (size_t)(tm.col0 / 16) * tm.L->rb * 256;
-        b.xs = tm.L->rb;
-      } else {  // (a derived [out][in] matrix, as dx() takes it)
-        b.p = tm.wv->m.t + (size_t)(tm.col0 / 16) * tm.wv->m.rbs * 256;
-        b.xs = tm.wv->m.rbs;
-      }
-      b.x1 = ncols;
-      b.r0 = roff;
-      b.r1 = roff + wout;
-      p.B.seg[t] = b;
+      p.B.seg[t] = wseg_t(tm, ncols, roff);
       roff += r16(wout);
       u.rd.push_back(tm.dz.id);
       u.rd.push_back(tm.L ? tm.L->res : tm.wv->id);
@@ -2546,6 +2544,13 @@ struct Engine {
     u.rd.push_back(a.id);
     return u;
   }
+
+  // Partial sums that an info-row entry (or a later op) reduces: the floats, how many, and the resource that
+  // orders their readers after the producer
+  struct LossPart {
+    float* p = nullptr;
+    int n = 0, id = -1;
+  };
 
   // Per-call options of the op builders below.  The default value is a plain layer: its output in both images,
   // tiles as the planner picks them.  A call names what it uses (a null operand leaves that feature off), and a
@@ -2569,6 +2574,15 @@ struct Engine {
     // split, so the stored output (the ReLU mask of the input gradient, the weight gradient's operand) is the
     // same floats as the consumer's copy, whatever the planner widens
     bool pl_src = false;
+    // EPI_MSE: the output is the gradient of mse_scale * sum (y - AvgL1Norm(mse_tgt))^2 over the batch rows; the
+    // per-tile loss partials are allocated here and returned in *loss
+    const View* mse_tgt = nullptr;
+    float mse_scale = 0.f;
+    // EPI_QHEAD: the output is dZ of this layer under a constant dL/dq = qhead_dq through the H -> 1 layer qhead;
+    // per-tile sums of Q - b (+ B b on tile 0) into the caller's slot loss->p, resource loss->id
+    const Layer* qhead = nullptr;
+    float qhead_dq = 0.f;
+    LossPart* loss = nullptr;  // (both: loss->n = the tiles written, one loss partial per 16-row block)
     FwdOpt() {}  // (user-provided, here and below: a default argument inside Engine cannot use the implicit one)
     FwdOpt& keep_pre(View* z, bool n_image = false) { return pre_out = z, pre_n = n_image, *this; }
     FwdOpt& norm() { return normed = true, *this; }
@@ -2580,6 +2594,8 @@ struct Engine {
     FwdOpt& keep_t(bool on) { return t = on, *this; }
     FwdOpt& no_t() { return keep_t(false); }
     FwdOpt& pl_source(bool on) { return pl_src = on, *this; }
+    FwdOpt& mse(const View* tgt, float scale, LossPart* out) { return mse_tgt = tgt, mse_scale = scale, loss = out, *this; }
+    FwdOpt& q_head(const Layer* l, float dq, LossPart* slot) { return qhead = l, qhead_dq = dq, loss = slot, *this; }
   };
   struct DxOpt {
     const View* into = nullptr;    // the output view (default: a new buffer)
@@ -2605,15 +2621,42 @@ struct Engine {
     float* gsq = nullptr;    // per-tile grad-square partials of the weights / the bias (dw_gsq_w / dw_gsq_b slots)
     float* gsq_b = nullptr;
     const View* nb_x = nullptr;  // kDwNb: dZ is the AvgL1Norm backward of (dz = g, nb_x), applied on load
+    // (TD3 policy steps) tau of the self-aliased target-policy Polyak fused into the Adam epilogue
+    // (AdamArgs::ptau), 0 elsewhere
+    float ptau = 0.f;
+    // (offline TD3 policy steps, kDwGs) lmbda, which the Adam epilogue multiplies the gradient by
+    // (GemmArgs::gscale; OP_BC mode 3, or mode 2 behind the standalone head, writes it), and its resource
+    const float* gscale = nullptr;
+    int gscale_id = -1;
     DwOpt() {}
     DwOpt& gsq_parts(const std::pair<float*, float*>& p) { return gsq = p.first, gsq_b = p.second, *this; }
     DwOpt& nb_defer(const View* x) { return nb_x = x, *this; }
+    DwOpt& polyak(float tau) { return ptau = tau, *this; }
+    DwOpt& grad_scale(const float* s, int id) { return gscale = s, gscale_id = id, *this; }
   };
   struct NormBwdOpt {
     bool n = true, t = true;  // output images, as DxOpt's
     NormBwdOpt() {}
     NormBwdOpt& no_t() { return t = false, *this; }
   };
+
+  // The tile plan of a forward or input-gradient GEMM, in one place for fwd() and dx().
+  // 64-row LDS-staged tiles (rle_plan wide; returns the tile width, 0 = off): a plain op (no in-tile prologue,
+  // fused head or row-wise epilogue), every row piece whole 64-row blocks, whole tile columns
+  int wide_tiles(bool plain, int N, const std::vector<int>& cuts) const {
+    bool wide = plan.wide && plain && N % plan.wide == 0;
+    for (size_t ci = 0; wide && ci + 1 < cuts.size(); ++ci) wide = (cuts[ci + 1] - cuts[ci]) % 64 == 0;
+    return wide ? plan.wide : 0;
+  }
+  // Tiles and workgroups of an M x N output in tn-wide tiles (wide: 64 rows per workgroup instead of 16)
+  static void set_tiles(Op& op, int M, int N, int tn, int wide) {
+    GemmArgs& g = op.gemm;
+    g.tn = wide ? wide : tn;
+    g.hot.wide = wide;
+    g.tiles_m = cdiv(M, kTileM);
+    g.tiles_n = cdiv(N, g.tn);
+    op.wg_count = (wide ? g.tiles_m / 4 : g.tiles_m) * g.tiles_n;
+  }
 
   View fwd(Prog& pg, const Layer& L, const std::vector<std::vector<View>>& ins, int M, int act, const FwdOpt& o = {}) {
     REQUIRE(ins.size() == L.seg_p.size(), "fwd: input segment count mismatch for " + L.wname);
@@ -2652,11 +2695,8 @@ struct Engine {
                           : o.pre && (o.pre->kind == 1 || o.pre->kind == 5)
                               ? (o.pl_src ? std::min(std::max(tq.first, pre_tn()), 32) : std::max(tq.first, pre_tn()))
                                                   : (o.pl_src ? std::min(tq.first, 32) : tq.first));
-    // 64-row LDS-staged tiles (rle_plan wide): every row piece whole 64-row blocks, 64-column blocks
-    bool wide = plan.wide && !o.sfu && !o.pre && !o.noise && L.out % plan.wide == 0;
-    for (size_t ci = 0; wide && ci + 1 < cuts.size(); ++ci) wide = (cuts[ci + 1] - cuts[ci]) % 64 == 0;
-    const int tn_w = wide ? plan.wide : tn;
-    const int tiles_n = cdiv(L.out, tn_w);
+    const int wide = wide_tiles(!o.sfu && !o.pre && !o.noise, L.out, cuts);
+    const int tiles_n = cdiv(L.out, wide ? wide : tn);
     View out = buf(M, L.out, true, o.t);
     if (o.sfu) {
       REQUIRE(!o.pre && !o.qdot && !o.normed && !o.noise && act == ACT_NONE && L.out <= 64, "fwd: SAC forward epilogue");
@@ -2693,6 +2733,22 @@ struct Engine {
       wr.push_back(out.qd_id);
       rd.push_back(o.qdot->res);
     }
+    if (o.loss) {  // EPI_MSE / EPI_QHEAD: one row piece, per-tile loss partials
+      REQUIRE(cuts.size() == 2 && !o.sfu && !o.pre && !o.qdot && !o.normed && !o.noise && !o.pre_out &&
+                  !o.mse_tgt != !o.qhead,
+              "fwd: a loss epilogue is a plain one-piece layer");
+      o.loss->n = cdiv(M, kTileM) * tiles_n;  // (wide: one loss partial per 16-row block too)
+      if (o.mse_tgt) {
+        o.loss->p = mem.make<float>(o.loss->n);
+        o.loss->id = next_id++;
+        rd.insert(rd.end(), {o.mse_tgt->id, o.mse_tgt->norm_id});
+      } else {
+        REQUIRE(L.seg_p.size() == 1 && ins[0][0].cols == L.seg_p[0] && ins[0][0].m.n && o.qhead->out == 1,
+                "qhead: operand layout");
+        rd.push_back(o.qhead->res);
+      }
+      wr.push_back(o.loss->id);
+    }
     if (o.noise) rd.push_back(o.noise->id);
     std::vector<Op> ops;
     for (size_t ci = 0; ci + 1 < cuts.size(); ++ci) {
@@ -2716,14 +2772,7 @@ struct Engine {
       }
       g.A.nseg = (int)ins.size();
       if (!o.wsegs) {
-        Seg w{};
-        w.p = P + L.wn_off;
-        w.xs = L.cb;
-        w.x0 = 0;
-        w.x1 = L.out;
-        w.r0 = 0;
-        w.r1 = L.K;
-        g.B.seg[0] = w;
+        g.B.seg[0] = wseg_n(L);
         g.B.nseg = 1;
       } else {  // one weight block per input segment, paired like a DX operand
         for (size_t q = 0; q < ins.size(); ++q) {
@@ -2741,10 +2790,7 @@ struct Engine {
       g.M = m;
       g.N = L.out;
       g.R = L.K;
-      g.tn = tn_w;
-      g.hot.wide = wide ? plan.wide : 0;
-      g.tiles_m = cdiv(m, kTileM);
-      g.tiles_n = tiles_n;
+      set_tiles(op, m, L.out, tn, wide);
       g.epi = EPI_STORE;
       g.act = act;
       g.out = out.sub(ra, m).m;
@@ -2766,6 +2812,23 @@ struct Engine {
         g.norm_out = qpart + ra;
         g.norm_ld = M;
       }
+      if (o.loss) {
+        g.loss_part = o.loss->p;
+        g.mvalid = Bv;
+      }
+      if (o.mse_tgt) {
+        g.epi = EPI_MSE;
+        g.tgt = o.mse_tgt->m;
+        g.tgt_norm = o.mse_tgt->nref();
+        g.mse_scale = o.mse_scale;
+      }
+      if (o.qhead) {
+        g.epi = EPI_QHEAD;
+        g.qw = P + o.qhead->wn_off;
+        g.qw_cbn = o.qhead->cb;
+        g.qb = bias(*o.qhead);
+        g.qscale = o.qhead_dq;
+      }
       if (o.noise && rb > o.noise_row0) {
         const int first = std::max(ra, o.noise_row0);  // first noised row (global)
         g.noise = o.noise->sub(first - o.noise_row0, rb - first).m;
@@ -2778,7 +2841,6 @@ struct Engine {
         g.prea = o.pre->a;
         if (o.pre->kind == 4) g.prea2 = o.pre->a2;
       }
-      op.wg_count = (wide ? g.tiles_m / 4 : g.tiles_m) * g.tiles_n;
       op.seq = tq.second;
       ops.push_back(op);
     }
@@ -2802,19 +2864,7 @@ struct Engine {
       REQUIRE(tm.dz.m.n && tm.col0 % 16 == 0 && (tm.L || (tm.wv && tm.wv->m.t)), "dx: operand layout");
       const int wout = tm.L ? tm.L->out : tm.wv->rows;
       g.A.seg[t] = seg_n(tm.dz, roff, roff + wout);
-      Seg b{};  // W[:, col0 : col0 + ncols] through the T image
-      if (tm.L) {
-        b.p = P + tm.L->wt_off + (size_t)(tm.col0 / 16) * tm.L->rb * 256;
-        b.xs = tm.L->rb;
-      } else {
-        b.p = tm.wv->m.t + (size_t)(tm.col0 / 16) * tm.wv->m.rbs * 256;
-        b.xs = tm.wv->m.rbs;
-      }
-      b.x0 = 0;
-      b.x1 = ncols;
-      b.r0 = roff;
-      b.r1 = roff + wout;
-      g.B.seg[t] = b;
+      g.B.seg[t] = wseg_t(tm, ncols, roff);
       roff += r16(wout);
       if (!(o.pre && (int)t == o.pre->a.seg)) rd.push_back(tm.dz.id);  // (else computed in-tile)
       rd.push_back(tm.L ? tm.L->res : tm.wv->id);
@@ -2824,16 +2874,12 @@ struct Engine {
     g.N = ncols;
     g.R = roff;
     const auto tq = choose_tn(M, ncols);
-    g.tn = o.pre && o.pre->kind == 3 ? std::max(tq.first, pl_tn())
-           : o.pre && o.pre->kind == 1 ? std::max(tq.first, pre_tn())
-                                   : (o.pl_src ? std::min(tq.first, 32) : tq.first);
+    const int tn = o.pre && o.pre->kind == 3 ? std::max(tq.first, pl_tn())
+                   : o.pre && o.pre->kind == 1 ? std::max(tq.first, pre_tn())
+                                           : (o.pl_src ? std::min(tq.first, 32) : tq.first);
     op.seq = tq.second;
-    // 64-row LDS-staged tiles (rle_plan wide): a plain or EPI_NBDOT input gradient over whole 64-row blocks
-    const bool wide = plan.wide && !o.pre && !o.head && !o.sbu && M % 64 == 0 && ncols % plan.wide == 0;
-    if (wide) g.tn = plan.wide;
-    g.hot.wide = wide ? plan.wide : 0;
-    g.tiles_m = cdiv(M, kTileM);
-    g.tiles_n = cdiv(ncols, g.tn);
+    // (wide: a plain or EPI_NBDOT input gradient)
+    set_tiles(op, M, ncols, tn, wide_tiles(!o.pre && !o.head && !o.sbu, ncols, {0, M}));
     g.epi = EPI_STORE;
     g.act = ACT_NONE;
     View out = o.into ? *o.into : buf(M, ncols, o.n, o.t);
@@ -2881,7 +2927,6 @@ struct Engine {
       rd.insert(rd.end(), o.sbu->rd.begin(), o.sbu->rd.end());
       wr.insert(wr.end(), o.sbu->wr.begin(), o.sbu->wr.end());
     }
-    op.wg_count = (wide ? g.tiles_m / 4 : g.tiles_m) * g.tiles_n;
     pg.add(op, rd, wr);
     return out;
   }
@@ -2952,11 +2997,11 @@ struct Engine {
     ad.bc2s = adam_bc2s_of(asc_set) + cnt;
     ad.lr = lr;
     ad.beta1 = 0.9f;
-    g.gscale = adam_gscale;
-    if (adam_gscale) {  // (the kDwGs variant: offline TD3's actor)
+    g.gscale = o.gscale;
+    if (o.gscale) {  // (the kDwGs variant: offline TD3's actor)
       REQUIRE(!nb_x, "dw: no gradient scale with a deferred AvgL1Norm backward");
       g.act = kDwGs;
-      rd.push_back(bc_s_id);
+      rd.push_back(o.gscale_id);
     }
     ad.beta2 = 0.999f;
     ad.omb1 = (float)(1.0 - 0.9);
@@ -2965,7 +3010,7 @@ struct Engine {
     ad.bias_col = cdiv(L.K, g.tn) * g.tn;
     ad.gsq = o.gsq;
     ad.gsq_b = o.gsq_b;
-    ad.ptau = adam_ptau;
+    ad.ptau = o.ptau;
     if (nb_x) {  // dZ = AvgL1Norm backward of (dz = g, x), applied on load (kDwNb)
       REQUIRE(dz.nbdot && nb_x->norm && nb_x->m.t && nb_x->rows >= Brows, "dw: deferred AvgL1Norm backward operands");
       g.act = kDwNb;
@@ -2990,13 +3035,7 @@ struct Engine {
     pg.add(op, rd, wr);
   }
 
-  // (TD3 policy steps) tau of the self-aliased target-policy Polyak fused into the actor's Adam
-  // epilogues (AdamArgs::ptau), 0 elsewhere
-  float adam_ptau = 0.f;
-  // (offline TD3 policy steps) lmbda, which the actor's Adam epilogues multiply the gradient by
-  // (GemmArgs::gscale; OP_BC mode 3, or mode 2 behind the standalone head, writes it), nullptr elsewhere
-  const float* adam_gscale = nullptr;
-  // (plan without RLE_FUSE_PIPOLYAK: the standalone OP_POLYAK over the policy instead, tests, A/B)
+  // (DwOpt::ptau; plan without RLE_FUSE_PIPOLYAK: the standalone OP_POLYAK over the policy instead, tests, A/B)
   bool pi_polyak_fused() const { return fused(RLE_FUSE_PIPOLYAK); }
 
   // The AvgL1Norm means of a normed view's rows (sale.py:11-13: mean |x| before the 1e-8 clamp), computed once
@@ -3417,22 +3456,168 @@ struct Engine {
     add_sampling(pg, sac, 0);
   }
 
-  void build_td7(Prog& pg, bool policy, int set) {
-    const int B2 = 2 * B;
-    Net& enc = net("encoder");
-    Net& fe = net("fixed_encoder");
-    Net& fet = net("fixed_encoder_target");
-    Net& pi = net("policy");
-    Net* q[2] = {&net("q1"), &net("q2")};
-    Net* tq[2] = {&net("target_q1"), &net("target_q2")};
-    const bool lap = cfg.use_lap;
-    const bool nbd = td7_nb_defer();
-    const bool qpart = td7_qdot();  // the loss head's q from EPI_QDOT partials
+  // What the phases of one step hand to each other.  build_td7 / build_mlp create one per step (begin_step) and
+  // pass it by reference, so nothing of a program under construction lives on the engine; what only two
+  // neighbouring phases share travels as a phase's return value instead.
+  struct StepBuild {
+    bool policy = false;
+    int set = 0;                      // the batch buffer set the step runs on
+    View s, s2;                       // its state and next-state rows
+    LossPart enc_loss, qloss, ploss;  // info row: TD7's encoder loss, the critic loss, the policy objective
+    int ploss_id2 = -1;               // (TD7: the second critic's q-head writes a loss resource of its own)
+    // behaviour cloning of an offline policy step (add_bc): e = dL_bc / d pi and (q_abs ..) I for the action
+    // gradient, the row blocks' sums of (pi - a)^2, the scalars {q_abs, lmbda}
+    View bc_e, bc_eye;
+    LossPart bc_part;
+    float* bc_s = nullptr;
+    int bc_s_id = -1;
+    // TD3 policy steps: per-tile grad-square partials of the actor; tensor t owns tiles [gsq_offs[t], gsq_offs[t+1])
+    float* gsq = nullptr;
+    std::vector<int> gsq_offs;
+  };
+  // The one place that selects a step's buffer set and Adam scalars (asc_set: read by dw() and the step end)
+  StepBuild begin_step(Prog& pg, bool policy, int set) {
     use_set(set);
     asc_set = set;
     add_adam_scalars(pg);
-    View s = ss.sub(0, B), s2 = ss.sub(B, B);
-    // ---- encoder phase (td7.py:246-257): online encoder on [s; s'] (one GEMM per layer)
+    StepBuild sb;
+    sb.policy = policy;
+    sb.set = set;
+    sb.s = ss.sub(0, B);
+    sb.s2 = ss.sub(B, B);
+    return sb;
+  }
+
+  // The critic loss head of a step (HEAD_TD7_LOSS / HEAD_MLP_LOSS with the target twins' last layer fused in): the
+  // buffers it writes and the fields and resources both algorithms share.  c / t: the last hidden layers of the
+  // critics / the target critics, dsrc: the derivative source of c's activation.  The caller adds its own fields
+  // and reads, then emits `op` or fuses it into the critics' input gradients (HeadUse).
+  struct LossHead {
+    Op op;
+    View dz[2], dq[2], prio;
+    std::vector<int> rd;
+  };
+  LossHead loss_head(StepBuild& sb, int mode, int tgt_mode, const View* c, const View* dsrc, const View* t,
+                     const Layer* const* qo, const Layer* const* tqo, bool fused_dx, bool lap) {
+    LossHead lh;
+    // (dZ of the critics' last hidden layers: with the fused head only their weight gradients read it, in the T image)
+    for (int n = 0; n < 2; ++n) lh.dz[n] = buf(B, H, !fused_dx, true);
+    for (int n = 0; n < 2; ++n) lh.dq[n] = buf(B, 1, false, true);
+    lh.prio = vec(B);
+    sb.qloss.n = cdiv(B, 4) * 4;
+    sb.qloss.p = mem.make<float>((size_t)sb.qloss.n);
+    lh.op = head_op(mode, Bv);
+    HeadArgs& h = lh.op.head;
+    set_head_twin(h, c[0], c[1], *qo[0], *qo[1]);
+    set_head_target(h, tgt_mode, t[0], t[1], *tqo[0], *tqo[1]);
+    h.reward = rw.p;
+    h.notdone = nd.p;
+    h.dact = actC;
+    h.lap = lap;
+    for (int n = 0; n < 2; ++n) {
+      h.dsrc[n] = dsrc[n].m;
+      h.dz[n] = lh.dz[n].m;
+      h.dq[n] = lh.dq[n].m;
+    }
+    h.loss_part = sb.qloss.p;
+    h.prio = lh.prio.p;
+    lh.rd = {c[0].id, c[1].id, qo[0]->res, qo[1]->res, t[0].id, t[1].id, tqo[0]->res, tqo[1]->res, rw.id, nd.id};
+    sb.qloss.id = next_id++;
+    return lh;
+  }
+  // The SAC fields of a head over the logpi rows from row0 on, and the two resources they read
+  void set_head_sac(HeadArgs& h, const View& logpi, int row0, std::vector<int>& rd) {
+    h.sac = 1;
+    h.logpi = logpi.p + row0;
+    h.log_alpha = alpha_src();
+    h.alpha_lin = cfg.tmp >= 0.f;
+    rd.push_back(logpi.id);
+    rd.push_back(R_LA);
+  }
+
+  // OP_BC, the behaviour-cloning term of an offline policy step, in its two ops.
+  // Mode 0 needs the actor output *v alone, so it runs many levels before the action gradient: e = dL_bc / d pi
+  // per row (sb.bc_e, scaled by lambda) and the row blocks' sums of (pi - a)^2 (sb.bc_part).
+  // The scalar op, one workgroup: q_abs into sb.bc_s[0] and its multiple of I into sb.bc_eye.  Mode 1 (TD7, reads no
+  // lambda): mean |cat Q| from the twins' row partials v[0], v[1] and their head layers qo.  Offline TD3, with
+  // lmbda = lambda / q_abs into sb.bc_s[1]: mode 3, mean |min Q| from the same operands, beside the fused policy
+  // head; mode 2, from the standalone policy head's |min| partials (sb.ploss), a level after it.
+  void add_bc(Prog& pg, StepBuild& sb, int mode, float lambda, const View* v, const Layer* const* qo = nullptr) {
+    Op op{};
+    op.kind = OP_BC;
+    BcArgs& b = op.bc;
+    b.mode = mode;
+    b.nvalid = Bv;
+    b.A = A;
+    b.lambda = lambda;
+    if (mode == 0) {
+      REQUIRE(A <= kThreads && v->m.n && act_in.m.n, "bc: operand layout");
+      sb.bc_e = buf(B, A, true, false);
+      sb.bc_part.n = cdiv(Bv, 16);
+      sb.bc_part.p = mem.make<float>((size_t)sb.bc_part.n);
+      sb.bc_part.id = next_id++;
+      b.pi = v->m;
+      b.a = act_in.m;
+      b.e = sb.bc_e.m;
+      b.part = sb.bc_part.p;
+      op.wg_count = sb.bc_part.n;
+      pg.add(op, {v->id, act_in.id}, {sb.bc_e.id, sb.bc_part.id});
+      return;
+    }
+    sb.bc_eye = buf(A, A, false, true);
+    sb.bc_s = mem.make<float>(4);
+    sb.bc_s_id = next_id++;
+    b.eye = sb.bc_eye.m;
+    b.out = sb.bc_s;
+    op.wg_count = 1;
+    if (mode == 2) {
+      b.qp[0] = sb.ploss.p + 1;
+      b.qp_n[0] = sb.ploss.n;
+      b.qp_ld = 4;
+      pg.add(op, {sb.ploss.id}, {sb.bc_eye.id, sb.bc_s_id});
+      return;
+    }
+    for (int n = 0; n < 2; ++n) {
+      b.qp[n] = v[n].qd;
+      b.qp_n[n] = v[n].qd_n;
+      b.qb[n] = bias(*qo[n]);
+    }
+    REQUIRE(v[0].qd && v[1].qd && v[0].qd_ld == v[1].qd_ld, "bc: q partial layout");
+    b.qp_ld = v[0].qd_ld;
+    pg.add(op, {v[0].qd_id, v[1].qd_id, qo[0]->res, qo[1]->res}, {sb.bc_eye.id, sb.bc_s_id});
+  }
+  // The offline tail of the info row, after the algorithm's three entries: TD7 [.., policy + bc term, bc, q_abs],
+  // TD3 [.., policy + bc term, norm/policy, train/bc, train/lmbda]; NaN on plain steps
+  void info_offline(StepEndArgs& a, std::vector<int>& rd, const StepBuild& sb) {
+    a.ninfo = 5;
+    if (!sb.policy) {
+      a.kind[3] = a.kind[4] = INFO_NAN;
+      return;
+    }
+    a.bcs = sb.bc_s;
+    info_sum(a, 3, sb.bc_part.p, sb.bc_part.n, 1, 1.f / ((float)Bv * (float)A));
+    if (algo == RLE_TD7) {
+      a.kind[2] = INFO_SUM_BC;
+      a.bc_lambda = cfg.bc_lambda;
+      info_sum(a, 4, sb.bc_s, 1, 1, 1.f);
+    } else {
+      a.kind[1] = INFO_SUM_BC3;  // lmbda * -mean(min Q) + bc
+      a.kind[4] = INFO_BCS1;
+    }
+    rd.push_back(sb.bc_s_id);
+    rd.push_back(sb.bc_part.id);
+  }
+  // TD7 offline mode (rle_config bc_lambda > 0); offline TD3 (rle_config_ext bc_alpha > 0, TD3+BC)
+  bool offline() const { return algo == RLE_TD7 && cfg.bc_lambda > 0.f; }
+  float bc_alpha = 0.f;
+  bool offline3() const { return algo == RLE_TD3 && bc_alpha > 0.f; }
+
+  // ---- TD7 (td7.py:287-332): build_td7 below is the list of these phases.
+  // Encoder update (td7.py:246-257): the online encoder on [s; s'] (one GEMM per layer), zsa3 with the MSE
+  // gradient against the normed zs' as its epilogue, then backward + Adam (optim_encoder, lr = policy_lr).
+  void td7_encoder_update(Prog& pg, StepBuild& sb) {
+    Net& enc = net("encoder");
+    const int B2 = 2 * B;
     View ez1, ez2;
     View eh1 = fwd(pg, enc.layers[0], {{ss}}, B2, actE, FwdOpt().keep_pre(&ez1));
     View eh2 = fwd(pg, enc.layers[1], {{eh1}}, B2, actE, FwdOpt().keep_pre(&ez2));
@@ -3441,96 +3626,75 @@ struct Engine {
     View ea1z, ea2z;
     View ea1 = fwd(pg, enc.layers[3], {{ezs}, {act_in}}, B, actE, FwdOpt().keep_pre(&ea1z));
     View ea2 = fwd(pg, enc.layers[4], {{ea1}}, B, actE, FwdOpt().keep_pre(&ea2z));
-    // zsa3 + MSE gradient vs zs_next (normed) fused
-    View ed3;
-    float* enc_loss = nullptr;
-    int enc_tiles = 0;
-    {
-      const Layer& L = enc.layers[5];
-      Op op{};
-      op.kind = OP_GEMM;
-      GemmArgs& g = op.gemm;
-      g.mode = GEMM_FWD;
-      g.A.seg[0] = seg_n(ea2, 0, L.K);
-      g.A.nseg = 1;
-      Seg w{};
-      w.p = P + L.wn_off;
-      w.xs = L.cb;
-      w.x1 = L.out;
-      w.r1 = L.K;
-      g.B.seg[0] = w;
-      g.B.nseg = 1;
-      g.M = B;
-      g.N = L.out;
-      g.R = L.K;
-      const auto tq = choose_tn(B, L.out);
-      const bool wide = plan.wide && B % 64 == 0 && L.out % plan.wide == 0;
-      g.tn = wide ? plan.wide : tq.first;
-      g.hot.wide = wide ? plan.wide : 0;
-      op.seq = tq.second;
-      g.tiles_m = cdiv(B, kTileM);
-      g.tiles_n = cdiv(L.out, g.tn);
-      g.epi = EPI_MSE;
-      g.bias = bias(L);
-      ed3 = buf(B, L.out);
-      g.out = ed3.m;
-      g.tgt = ezs2.m;
-      g.tgt_norm = ezs2.nref();
-      enc_tiles = g.tiles_m * g.tiles_n;
-      enc_loss = mem.make<float>(enc_tiles);
-      g.loss_part = enc_loss;
-      g.mse_scale = 1.f / (float)((long long)Bv * Z);  // (mean over the B x zs_dim zsa, td7.py:253)
-      g.mvalid = Bv;
-      op.wg_count = (wide ? g.tiles_m / 4 : g.tiles_m) * g.tiles_n;
-      pg.add(op, {ea2.id, L.res, ezs2.id, ezs2.norm_id}, {ed3.id, loss_id_enc = next_id++});
-    }
-    // encoder backward + Adam (optim_encoder, lr = policy_lr)
-    {
-      View d2 = dx(pg, {{ed3, &enc.layers[5], 0}}, H, B, actE, &ea2z);
-      dw(pg, enc.layers[5], ed3, {ea2}, B, CNT_ADAM_ENC, cfg.policy_lr);
-      View d1 = dx(pg, {{d2, &enc.layers[4], 0}}, H, B, actE, &ea1z);
-      dw(pg, enc.layers[4], d2, {ea1}, B, CNT_ADAM_ENC, cfg.policy_lr);
-      View gzs = dx(pg, {{d1, &enc.layers[3], 0}}, Z, B, DxOpt().no_t());  // (read by the norm backward only)
-      dw(pg, enc.layers[3], d1, {ezs, act_in}, B, CNT_ADAM_ENC, cfg.policy_lr);
-      View dx3 = normbwd(pg, gzs, ex3.sub(0, B));
-      View ez2s = ez2.sub(0, B), ez1s = ez1.sub(0, B);
-      View dh2 = dx(pg, {{dx3, &enc.layers[2], 0}}, H, B, actE, &ez2s);
-      dw(pg, enc.layers[2], dx3, {eh2.sub(0, B)}, B, CNT_ADAM_ENC, cfg.policy_lr);
-      View dh1 = dx(pg, {{dh2, &enc.layers[1], 0}}, H, B, actE, &ez1s);
-      dw(pg, enc.layers[1], dh2, {eh1.sub(0, B)}, B, CNT_ADAM_ENC, cfg.policy_lr);
-      dw(pg, enc.layers[0], dh1, {s}, B, CNT_ADAM_ENC, cfg.policy_lr);
-    }
-    // ---- fixed encoder on s, fixed target encoder on s'
+    const float mean = 1.f / (float)((long long)Bv * Z);  // (mean over the B x zs_dim zsa, td7.py:253)
+    View ed3 = fwd(pg, enc.layers[5], {{ea2}}, B, ACT_NONE, FwdOpt().mse(&ezs2, mean, &sb.enc_loss));
+    View d2 = dx(pg, {{ed3, &enc.layers[5], 0}}, H, B, actE, &ea2z);
+    dw(pg, enc.layers[5], ed3, {ea2}, B, CNT_ADAM_ENC, cfg.policy_lr);
+    View d1 = dx(pg, {{d2, &enc.layers[4], 0}}, H, B, actE, &ea1z);
+    dw(pg, enc.layers[4], d2, {ea1}, B, CNT_ADAM_ENC, cfg.policy_lr);
+    View gzs = dx(pg, {{d1, &enc.layers[3], 0}}, Z, B, DxOpt().no_t());  // (read by the norm backward only)
+    dw(pg, enc.layers[3], d1, {ezs, act_in}, B, CNT_ADAM_ENC, cfg.policy_lr);
+    View dx3 = normbwd(pg, gzs, ex3.sub(0, B));
+    View ez2s = ez2.sub(0, B), ez1s = ez1.sub(0, B);
+    View dh2 = dx(pg, {{dx3, &enc.layers[2], 0}}, H, B, actE, &ez2s);
+    dw(pg, enc.layers[2], dx3, {eh2.sub(0, B)}, B, CNT_ADAM_ENC, cfg.policy_lr);
+    View dh1 = dx(pg, {{dh2, &enc.layers[1], 0}}, H, B, actE, &ez1s);
+    dw(pg, enc.layers[1], dh2, {eh1.sub(0, B)}, B, CNT_ADAM_ENC, cfg.policy_lr);
+    dw(pg, enc.layers[0], dh1, {sb.s}, B, CNT_ADAM_ENC, cfg.policy_lr);
+  }
+  // Fixed encoder on s, fixed target encoder on s', and the actor on [s; s'] (the target policy aliases the
+  // policy, Q1).  The later phases read:
+  struct Td7Actor {
+    View fzs, tzs, fzsa;         // zs of s (fixed encoder) and of s' (fixed target encoder); zsa of (s, a)
+    View ap0, ap1, ap2;          // the actor's hidden layers on [s; s'] ...
+    View ap1z, ap2z;             // ... and an ELU actor's pre-activations, for the policy backward: ELU' = exp(z)
+    View a_pi, a_next;           // pi(s); the smoothed target action (pre: layout only)
+    bool prea = false;           // a' is recomputed in-tile by the target branch's first layers (pre-GEMM pn1)
+    PreUse pn1;
+    const PreUse* pnext() const { return prea ? &pn1 : nullptr; }
+  };
+  Td7Actor td7_fixed_and_actor(Prog& pg, const StepBuild& sb) {
+    Net& fe = net("fixed_encoder");
+    Net& fet = net("fixed_encoder_target");
+    Net& pi = net("policy");
+    const int B2 = 2 * B;
+    Td7Actor o;
     // forward-only outputs (no weight gradient reads them); fzs and fzsa, which the critics' and the actor's
     // weight gradients read, keep both images
     const FwdOpt fo = FwdOpt().no_t();
-    View fh1 = fwd(pg, fe.layers[0], {{s}}, B, actE, fo);
+    View fh1 = fwd(pg, fe.layers[0], {{sb.s}}, B, actE, fo);
     View fh2 = fwd(pg, fe.layers[1], {{fh1}}, B, actE, fo);
-    View fzs = fwd(pg, fe.layers[2], {{fh2}}, B, ACT_NONE, FwdOpt().norm());
-    View th1 = fwd(pg, fet.layers[0], {{s2}}, B, actE, fo);
+    o.fzs = fwd(pg, fe.layers[2], {{fh2}}, B, ACT_NONE, FwdOpt().norm());
+    View th1 = fwd(pg, fet.layers[0], {{sb.s2}}, B, actE, fo);
     View th2 = fwd(pg, fet.layers[1], {{th1}}, B, actE, fo);
-    View tzs = fwd(pg, fet.layers[2], {{th2}}, B, ACT_NONE, FwdOpt(fo).norm());
-    View fa1 = fwd(pg, fe.layers[3], {{fzs}, {act_in}}, B, actE, fo);
+    o.tzs = fwd(pg, fet.layers[2], {{th2}}, B, ACT_NONE, FwdOpt(fo).norm());
+    View fa1 = fwd(pg, fe.layers[3], {{o.fzs}, {act_in}}, B, actE, fo);
     View fa2 = fwd(pg, fe.layers[4], {{fa1}}, B, actE, fo);
-    View fzsa = fwd(pg, fe.layers[5], {{fa2}}, B, ACT_NONE);
-    // ---- actor on [s; s'] (target policy aliases the policy, Q1)
-    View ap0 = fwd(pg, pi.layers[0], {{ss}}, B2, ACT_NONE, FwdOpt().norm());
-    // (an ELU actor keeps its pre-activations for the policy backward: ELU' = exp(z))
-    View ap1z, ap2z;
+    o.fzsa = fwd(pg, fe.layers[5], {{fa2}}, B, ACT_NONE);
+    o.ap0 = fwd(pg, pi.layers[0], {{ss}}, B2, ACT_NONE, FwdOpt().norm());
     const bool pz = actP == ACT_ELU;
-    View ap1 = fwd(pg, pi.layers[1], {{ap0}, {fzs, tzs}}, B2, actP, FwdOpt().keep_pre(pz ? &ap1z : nullptr));
-    View ap2 = fwd(pg, pi.layers[2], {{ap1}}, B2, actP, FwdOpt().keep_pre(pz ? &ap2z : nullptr));
+    o.ap1 = fwd(pg, pi.layers[1], {{o.ap0}, {o.fzs, o.tzs}}, B2, actP, FwdOpt().keep_pre(pz ? &o.ap1z : nullptr));
+    o.ap2 = fwd(pg, pi.layers[2], {{o.ap1}}, B2, actP, FwdOpt().keep_pre(pz ? &o.ap2z : nullptr));
     // a' = clamp(pi(s', zs') + noise) only feeds the target branch's first layers, which
     // recompute it in-tile (pre-GEMM): the actor output layer runs on the s rows alone
-    const bool prea = actor_pre();
-    View actv = prea ? fwd(pg, pi.layers[3], {{ap2.sub(0, B)}}, B, ACT_TANH)
-                     : fwd(pg, pi.layers[3], {{ap2}}, B2, ACT_TANH, FwdOpt().noised(&eps, B));
-    View a_pi = actv.sub(0, B), a_next = prea ? a_pi : actv.sub(B, B);  // (pre: layout only)
-    const View ap2n = ap2.sub(B, B);
-    const PreUse pn1 = prea ? pre_actor_fwd(pi.layers[3], ap2n, &eps, 1) : PreUse{};
-    const PreUse* pnext = prea ? &pn1 : nullptr;
-    // ---- target: zsa' and target critics (forward only: fo)
-    View ta1 = fwd(pg, fet.layers[3], {{tzs}, {a_next}}, B, actE, FwdOpt(fo).pre_gemm(pnext));
+    o.prea = actor_pre();
+    View actv = o.prea ? fwd(pg, pi.layers[3], {{o.ap2.sub(0, B)}}, B, ACT_TANH)
+                       : fwd(pg, pi.layers[3], {{o.ap2}}, B2, ACT_TANH, FwdOpt().noised(&eps, B));
+    o.a_pi = actv.sub(0, B);
+    o.a_next = o.prea ? o.a_pi : actv.sub(B, B);
+    if (o.prea) o.pn1 = pre_actor_fwd(pi.layers[3], o.ap2.sub(B, B), &eps, 1);
+    return o;
+  }
+  // Target branch (forward only): zsa' and the target critics' last hidden layers on (s', a')
+  struct TwinViews {
+    View v[2];
+  };
+  TwinViews td7_target(Prog& pg, const StepBuild& sb, const Td7Actor& ac) {
+    Net& fet = net("fixed_encoder_target");
+    Net* tq[2] = {&net("target_q1"), &net("target_q2")};
+    const FwdOpt fo = FwdOpt().no_t();
+    const PreUse* pnext = ac.pnext();
+    View ta1 = fwd(pg, fet.layers[3], {{ac.tzs}, {ac.a_next}}, B, actE, FwdOpt(fo).pre_gemm(pnext));
     View ta2 = fwd(pg, fet.layers[4], {{ta1}}, B, actE, fo);
     // zsa' = zsa3(ta2) only feeds the target critics' first hidden layer, a linear map:
     // with `fold`, tq.q1[:, zsa block] x fet.zsa3 is precomputed (add_target_fold) and the
@@ -3538,322 +3702,205 @@ struct Engine {
     const bool fold = td7_fold();
     View tzsa;
     if (!fold) tzsa = fwd(pg, fet.layers[5], {{ta2}}, B, ACT_NONE, fo);
-    View th[2];
+    TwinViews th;
     for (int n = 0; n < 2; ++n) {
-      View t01 = fwd(pg, tq[n]->layers[0], {{s2}, {a_next}}, B, ACT_NONE, FwdOpt(fo).norm().pre_gemm(pnext));
+      View t01 = fwd(pg, tq[n]->layers[0], {{sb.s2}, {ac.a_next}}, B, ACT_NONE, FwdOpt(fo).norm().pre_gemm(pnext));
       View t1;
       if (fold) {  // fixed_encoder_target.zsa3 folded into the zsa block (tfold_w / tfold_b)
         const Layer& L1 = tq[n]->layers[1];
         const std::vector<WSeg> ws{wblock(L1, 0), {tfold_w[n].m.n, tfold_w[n].m.cbn, tfold_w[n].id},
                                    wblock(L1, L1.seg_p[0] + L1.seg_p[1])};
-        t1 = fwd(pg, L1, {{t01}, {ta2}, {tzs}}, B, actC, FwdOpt(fo).wblocks(&ws, &tfold_b[n]));
+        t1 = fwd(pg, L1, {{t01}, {ta2}, {ac.tzs}}, B, actC, FwdOpt(fo).wblocks(&ws, &tfold_b[n]));
       } else {
-        t1 = fwd(pg, tq[n]->layers[1], {{t01}, {tzsa}, {tzs}}, B, actC, fo);
+        t1 = fwd(pg, tq[n]->layers[1], {{t01}, {tzsa}, {ac.tzs}}, B, actC, fo);
       }
-      th[n] = fwd(pg, tq[n]->layers[2], {{t1}}, B, actC, FwdOpt(fo).q_dot(qpart ? &tq[n]->layers[3] : nullptr));
+      th.v[n] = fwd(pg, tq[n]->layers[2], {{t1}}, B, actC, FwdOpt(fo).q_dot(td7_qdot() ? &tq[n]->layers[3] : nullptr));
     }
-    // ---- online critics on (s, a, zsa_f, zs_f)
-    View c01[2], c1[2], c2[2], c1z[2], c2z[2];
+    return th;
+  }
+  // Online critics on (s, a, zsa_f, zs_f) and the loss head (td7.py:211-218; y per row from the target twins,
+  // then the loss), the priority update and the next step's batch.  The backward reads:
+  struct Td7Critics {
+    View c01[2], c1[2], c2[2], c1z[2];  // the layers' outputs and the first hidden layer's pre-activation
+    View dz2[2], dq[2];                 // the head's gradients: dZ of the last hidden layer, dq
+    bool hdx = false;                   // the head ran inside the DX of each critic's second hidden layer, ...
+    View d1f[2];                        // ... which gave dZ of the first
+  };
+  Td7Critics td7_critics(Prog& pg, StepBuild& sb, const Td7Actor& ac, const TwinViews& th) {
+    Net* q[2] = {&net("q1"), &net("q2")};
+    Net* tq[2] = {&net("target_q1"), &net("target_q2")};
+    const bool qpart = td7_qdot();  // the loss head's q from EPI_QDOT partials
+    Td7Critics o;
+    View c2z[2];
     for (int n = 0; n < 2; ++n) {
-      c01[n] = fwd(pg, q[n]->layers[0], {{s}, {act_in}}, B, ACT_NONE, FwdOpt().norm());
-      c1[n] = fwd(pg, q[n]->layers[1], {{c01[n]}, {fzsa}, {fzs}}, B, actC, FwdOpt().keep_pre(&c1z[n]));
-      c2[n] = fwd(pg, q[n]->layers[2], {{c1[n]}}, B, actC,
-                  FwdOpt().keep_pre(&c2z[n], true).q_dot(qpart ? &q[n]->layers[3] : nullptr));
+      o.c01[n] = fwd(pg, q[n]->layers[0], {{sb.s}, {act_in}}, B, ACT_NONE, FwdOpt().norm());
+      o.c1[n] = fwd(pg, q[n]->layers[1], {{o.c01[n]}, {ac.fzsa}, {ac.fzs}}, B, actC, FwdOpt().keep_pre(&o.c1z[n]));
+      o.c2[n] = fwd(pg, q[n]->layers[2], {{o.c1[n]}}, B, actC,
+                    FwdOpt().keep_pre(&c2z[n], true).q_dot(qpart ? &q[n]->layers[3] : nullptr));
     }
-    const bool hdx = td7_headdx() && qpart;  // (the fused head reads q partials only)
-    // (dZ of the critics' last hidden layers: with the fused head only their weight gradients
-    // read it, in the T image)
-    View dz2[2] = {buf(B, H, !hdx, true), buf(B, H, !hdx, true)},
-         dq[2] = {buf(B, 1, false, true), buf(B, 1, false, true)};
-    View prio = vec(B);
-    const int hw = cdiv(B, 4);
-    qloss_part = mem.make<float>((size_t)hw * 4);
-    View d1f[2];  // (hdx) dZ of each critic's first hidden layer from the fused head + DX
-    {
-      // target head (td7.py:211-218) fused: y per row from the target twins, then the loss
-      Op op = head_op(HEAD_TD7_LOSS, Bv);
-      HeadArgs& h = op.head;
-      set_head_twin(h, c2[0], c2[1], q[0]->layers[3], q[1]->layers[3]);
-      set_head_target(h, HEAD_TD7_TARGET, th[0], th[1], tq[0]->layers[3], tq[1]->layers[3]);
-      h.reward = rw.p;
-      h.notdone = nd.p;
-      h.vmax_key = &ctrl->vmax_key;
-      h.vmin_key = &ctrl->vmin_key;
-      h.vt = ctrl->vt;
-      h.dsrc[0] = c2z[0].m;
-      h.dsrc[1] = c2z[1].m;
-      h.dact = actC;
-      h.lap = lap;
-      h.dz[0] = dz2[0].m;
-      h.dz[1] = dz2[1].m;
-      h.dq[0] = dq[0].m;
-      h.dq[1] = dq[1].m;
-      h.loss_part = qloss_part;
-      h.prio = prio.p;
-      std::vector<int> qrd;
-      if (qpart) {
-        for (int n = 0; n < 2; ++n) {
-          h.qp[n] = c2[n].qd;
-          h.tp[n] = th[n].qd;
-          h.qp_n[n] = c2[n].qd_n;
-          h.tp_n[n] = th[n].qd_n;
-          qrd.push_back(c2[n].qd_id);
-          qrd.push_back(th[n].qd_id);
-        }
-        h.qp_ld = c2[0].qd_ld;
-        h.tp_ld = th[0].qd_ld;
-        REQUIRE(c2[1].qd_ld == h.qp_ld && th[1].qd_ld == h.tp_ld && h.qp_n[0] <= 64 && h.qp_n[1] <= 64 &&
-                    h.tp_n[0] <= 64 && h.tp_n[1] <= 64,
-                "head: q partial layout");
-      }
-      qloss_id = next_id++;
-      if (!hdx) {
-        std::vector<int> rd{c2[0].id, c2[1].id, c2z[0].id, c2z[1].id, q[0]->layers[3].res, q[1]->layers[3].res,
-                            th[0].id, th[1].id, tq[0]->layers[3].res, tq[1]->layers[3].res, rw.id, nd.id, R_VT};
-        rd.insert(rd.end(), qrd.begin(), qrd.end());
-        pg.add(op, rd, {dz2[0].id, dz2[1].id, dq[0].id, dq[1].id, prio.id, qloss_id, R_VKEYS});
-      } else {
-        // the head runs inside the DX of each critic's second hidden layer (one level fewer on
-        // the critic chain); critic 0's op stores the priorities, loss partials and value bounds
-        for (int n = 0; n < 2; ++n) {
-          HeadUse hu{h, n,
-                     {c2[0].id, c2[1].id, q[0]->layers[3].res, q[1]->layers[3].res, th[0].id, th[1].id,
-                      tq[0]->layers[3].res, tq[1]->layers[3].res, rw.id, nd.id, R_VT},
-                     {dz2[n].id, dq[n].id}};
-          if (n == 0) hu.wr.insert(hu.wr.end(), {prio.id, qloss_id, R_VKEYS});
-          hu.rd.insert(hu.rd.end(), qrd.begin(), qrd.end());
-          d1f[n] = dx(pg, {{c2z[n], &q[n]->layers[2], 0}}, H, B, actC, &c1z[n], DxOpt().head_use(&hu));
-        }
+    o.hdx = td7_headdx() && qpart;  // (the fused head reads q partials only)
+    const Layer *qo[2] = {&q[0]->layers[3], &q[1]->layers[3]}, *tqo[2] = {&tq[0]->layers[3], &tq[1]->layers[3]};
+    LossHead lh = loss_head(sb, HEAD_TD7_LOSS, HEAD_TD7_TARGET, o.c2, c2z, th.v, qo, tqo, o.hdx, cfg.use_lap);
+    HeadArgs& h = lh.op.head;
+    h.vmax_key = &ctrl->vmax_key;
+    h.vmin_key = &ctrl->vmin_key;
+    h.vt = ctrl->vt;
+    lh.rd.push_back(R_VT);
+    if (qpart) {
+      set_head_parts(h, o.c2, th.v, lh.rd);
+      REQUIRE(h.qp_n[0] <= 64 && h.qp_n[1] <= 64 && h.tp_n[0] <= 64 && h.tp_n[1] <= 64, "head: q partial layout");
+    }
+    for (int n = 0; n < 2; ++n) o.dz2[n] = lh.dz[n], o.dq[n] = lh.dq[n];
+    if (!o.hdx) {
+      std::vector<int> rd = lh.rd;
+      rd.insert(rd.end(), {c2z[0].id, c2z[1].id});
+      pg.add(lh.op, rd, {lh.dz[0].id, lh.dz[1].id, lh.dq[0].id, lh.dq[1].id, lh.prio.id, sb.qloss.id, R_VKEYS});
+    } else {
+      // the head runs inside the DX of each critic's second hidden layer (one level fewer on
+      // the critic chain); critic 0's op stores the priorities, loss partials and value bounds
+      for (int n = 0; n < 2; ++n) {
+        HeadUse hu{h, n, lh.rd, {lh.dz[n].id, lh.dq[n].id}};
+        if (n == 0) hu.wr.insert(hu.wr.end(), {lh.prio.id, sb.qloss.id, R_VKEYS});
+        o.d1f[n] = dx(pg, {{c2z[n], &q[n]->layers[2], 0}}, H, B, actC, &o.c1z[n], DxOpt().head_use(&hu));
       }
     }
-    add_update_and_prefetch(pg, false, set, lap, prio);
-    for (int n = 0; n < 2; ++n) {  // critic backward + Adam (optim_q_fns spans q1 + q2)
-      Net& Q = *q[n];
-      dw(pg, Q.layers[3], dq[n], {c2[n]}, B, CNT_ADAM_Q, cfg.critic_lr);
-      View d1 = hdx ? d1f[n] : dx(pg, {{dz2[n], &Q.layers[2], 0}}, H, B, actC, &c1z[n]);
-      dw(pg, Q.layers[2], dz2[n], {c1[n]}, B, CNT_ADAM_Q, cfg.critic_lr);
+    add_update_and_prefetch(pg, false, sb.set, cfg.use_lap, lh.prio);
+    return o;
+  }
+  // Critic backward + Adam (optim_q_fns spans q1 + q2)
+  void td7_critic_backward(Prog& pg, const StepBuild& sb, const Td7Actor& ac, const Td7Critics& cr) {
+    const bool nbd = td7_nb_defer();
+    for (int n = 0; n < 2; ++n) {
+      Net& Q = net(n ? "q2" : "q1");
+      dw(pg, Q.layers[3], cr.dq[n], {cr.c2[n]}, B, CNT_ADAM_Q, cfg.critic_lr);
+      View d1 = cr.hdx ? cr.d1f[n] : dx(pg, {{cr.dz2[n], &Q.layers[2], 0}}, H, B, actC, &cr.c1z[n]);
+      dw(pg, Q.layers[2], cr.dz2[n], {cr.c1[n]}, B, CNT_ADAM_Q, cfg.critic_lr);
       // (read by the weight gradient / the norm backward only: the T / the N image alone)
-      View g01 = dx(pg, {{d1, &Q.layers[1], 0}}, H, B, DxOpt().nb_defer(nbd ? &c01[n] : nullptr).images(!nbd, nbd));
-      dw(pg, Q.layers[1], d1, {c01[n], fzsa, fzs}, B, CNT_ADAM_Q, cfg.critic_lr);
+      View g01 = dx(pg, {{d1, &Q.layers[1], 0}}, H, B, DxOpt().nb_defer(nbd ? &cr.c01[n] : nullptr).images(!nbd, nbd));
+      dw(pg, Q.layers[1], d1, {cr.c01[n], ac.fzsa, ac.fzs}, B, CNT_ADAM_Q, cfg.critic_lr);
       if (nbd) {  // AvgL1Norm backward deferred into the weight-gradient GEMM (kDwNb)
-        dw(pg, Q.layers[0], g01, {s, act_in}, B, CNT_ADAM_Q, cfg.critic_lr, DwOpt().nb_defer(&c01[n]));
+        dw(pg, Q.layers[0], g01, {sb.s, act_in}, B, CNT_ADAM_Q, cfg.critic_lr, DwOpt().nb_defer(&cr.c01[n]));
       } else {
-        View dx01 = normbwd(pg, g01, c01[n]);
-        dw(pg, Q.layers[0], dx01, {s, act_in}, B, CNT_ADAM_Q, cfg.critic_lr);
+        View dx01 = normbwd(pg, g01, cr.c01[n]);
+        dw(pg, Q.layers[0], dx01, {sb.s, act_in}, B, CNT_ADAM_Q, cfg.critic_lr);
       }
     }
-    ploss_part = nullptr;
-    if (policy) {  // td7.py:259-276 with the updated critics (no weight gradient of these layers)
-      View pa1z, pa2z;
-      View pa1 = fwd(pg, fe.layers[3], {{fzs}, {a_pi}}, B, actE, FwdOpt(fo).keep_pre(&pa1z));
-      View pa2 = fwd(pg, fe.layers[4], {{pa1}}, B, actE, FwdOpt(fo).keep_pre(&pa2z));
-      View pzsa = fwd(pg, fe.layers[5], {{pa2}}, B, ACT_NONE, fo);
-      View p01[2], p1[2], p1z[2], dzp2[2];
-      for (int n = 0; n < 2; ++n) {
-        p01[n] = fwd(pg, q[n]->layers[0], {{s}, {a_pi}}, B, ACT_NONE, FwdOpt(fo).norm());
-        p1[n] = fwd(pg, q[n]->layers[1], {{p01[n]}, {pzsa}, {fzs}}, B, actC, FwdOpt(fo).keep_pre(&p1z[n]));
-      }
-      // q2 + q3 + dL/dQ = -1/(2B) fused (EPI_QHEAD): dZ of q2 straight from the GEMM
-      ploss_id = next_id++;  // one loss resource per critic: the two heads share a level
-      ploss_id2 = next_id++;
-      ploss_part = mem.make<float>((size_t)(qhead_tiles(q[0]->layers[2]) + qhead_tiles(q[1]->layers[2])));
-      ploss_n = 0;
-      for (int n = 0; n < 2; ++n) {
-        int nt = 0;
-        dzp2[n] = fwd_qhead(pg, q[n]->layers[2], q[n]->layers[3], p1[n], B, -0.5f / (float)Bv, ploss_part + ploss_n,
-                            &nt, n ? ploss_id2 : ploss_id);
-        ploss_n += nt;
-      }
-      // ---- offline (rle_config bc_lambda): + lmbda * mean|cat Q|.detach() * mse(pi(s), a).  dL/dq stays
-      // -1/(2B) (q_abs is detached), so the q-heads above are the online ones.  The per-row q for q_abs: the
-      // same layers once more with the EPI_QDOT epilogue, beside the q-heads (same level, nothing waits for
-      // them but OP_BC); OP_BC a level later forms q_abs, bc and e = dL_bc / d pi, which the action gradient
-      // below reads several levels on.
-      View bc_e, bc_eye;
-      bc_s = nullptr;
-      if (offline()) {
-        REQUIRE(A <= kThreads && a_pi.m.n && act_in.m.n, "bc: operand layout");
-        // (mode 0: needs the actor output alone, so it runs many levels before the action gradient)
-        bc_e = buf(B, A, true, false);
-        bc_part_n = cdiv(Bv, 16);
-        bc_part = mem.make<float>((size_t)bc_part_n);
-        bc_part_id = next_id++;
-        {
-          Op op{};
-          op.kind = OP_BC;
-          BcArgs& b = op.bc;
-          b.mode = 0;
-          b.nvalid = Bv;
-          b.A = A;
-          b.lambda = cfg.bc_lambda;
-          b.pi = a_pi.m;
-          b.a = act_in.m;
-          b.e = bc_e.m;
-          b.part = bc_part;
-          op.wg_count = bc_part_n;
-          pg.add(op, {a_pi.id, act_in.id}, {bc_e.id, bc_part_id});
-        }
-        View pq[2];
-        for (int n = 0; n < 2; ++n)
-          pq[n] = fwd(pg, q[n]->layers[2], {{p1[n]}}, B, actC, FwdOpt(fo).q_dot(&q[n]->layers[3]));
-        bc_eye = buf(A, A, false, true);
-        bc_s = mem.make<float>(4);
-        bc_s_id = next_id++;
-        Op op{};
-        op.kind = OP_BC;
-        BcArgs& b = op.bc;
-        b.mode = 1;
-        for (int n = 0; n < 2; ++n) {
-          b.qp[n] = pq[n].qd;
-          b.qp_n[n] = pq[n].qd_n;
-          b.qb[n] = bias(q[n]->layers[3]);
-        }
-        REQUIRE(pq[0].qd_ld == pq[1].qd_ld, "bc: q partial layout");
-        b.qp_ld = pq[0].qd_ld;
-        b.nvalid = Bv;
-        b.A = A;
-        b.eye = bc_eye.m;
-        b.out = bc_s;
-        op.wg_count = 1;
-        pg.add(op, {pq[0].qd_id, pq[1].qd_id, q[0]->layers[3].res, q[1]->layers[3].res}, {bc_eye.id, bc_s_id});
-      }
-      View dzp1[2], dxp01[2];
-      const DxOpt po = DxOpt().no_t();  // (no weight gradient of the critics or the fixed encoder in the policy pass)
-      for (int n = 0; n < 2; ++n) {
-        dzp1[n] = dx(pg, {{dzp2[n], &q[n]->layers[2], 0}}, H, B, actC, &p1z[n], po);
-        View g = dx(pg, {{dzp1[n], &q[n]->layers[1], 0}}, H, B, po);
-        dxp01[n] = normbwd(pg, g, p01[n], NormBwdOpt().no_t());
-      }
-      // grad wrt zsa from both critics (q1 input columns [H, 2H))
-      View dpa2;
-      if (fold) {  // d zsa -> d pa2 through zsa3 folded: G_n = q_n.q1[:, zsa block] x fe.zsa3 (updated critics)
-        View G[2];
-        for (int n = 0; n < 2; ++n)
-          G[n] = dx(pg, {{wview_n(q[n]->layers[1], Hp, H), &fe.layers[5], 0}}, H, H);  // (a T-image operand below)
-        dpa2 = dx(pg, {{dzp1[0], nullptr, 0, &G[0]}, {dzp1[1], nullptr, 0, &G[1]}}, H, B, actE, &pa2z, po);
-      } else {
-        View gzsa = dx(pg, {{dzp1[0], &q[0]->layers[1], Hp}, {dzp1[1], &q[1]->layers[1], Hp}}, Z, B);
-        dpa2 = dx(pg, {{gzsa, &fe.layers[5], 0}}, H, B, actE, &pa2z);
-      }
-      View dpa1 = dx(pg, {{dpa2, &fe.layers[4], 0}}, H, B, actE, &pa1z, po);
-      // d action = sum of three paths, then tanh' (actor output)
-      std::vector<DxTerm> t3{
-          {dxp01[0], &q[0]->layers[0], Sp}, {dxp01[1], &q[1]->layers[0], Sp}, {dpa1, &fe.layers[3], Zp}};
-      // (offline: e0 x (q_abs I), the behaviour-cloning gradient wrt pi, one more reduction segment ahead of
-      // tanh' -- in the in-tile recomputation below as well, so RLE_FUSE_PRE stays)
-      if (offline()) t3.push_back({bc_e, nullptr, 0, &bc_eye});
-      View dl3 = dx(pg, t3, A, B, ACT_TANH, &a_pi);
-      const PreUse p3 = prea ? pre_actor_dx(t3, A, a_pi, 0) : PreUse{};  // dl2 recomputes dl3 in-tile
-      // input-grads through a layer are emitted BEFORE its Adam update so the
-      // scheduler orders them against the pre-update weights (as autograd does)
-      View ap2s = ap2.sub(0, B), ap1s = ap1.sub(0, B);
-      const View ap2zs = actP == ACT_ELU ? ap2z.sub(0, B) : View{}, ap1zs = actP == ACT_ELU ? ap1z.sub(0, B) : View{};
-      View dl2 = dx(pg, {{dl3, &pi.layers[3], 0}}, H, B, actP, dsrc_of(actP, ap2s, ap2zs),
-                    DxOpt().pre_gemm(prea ? &p3 : nullptr));
-      dw(pg, pi.layers[3], dl3, {ap2s}, B, CNT_ADAM_PI, cfg.policy_lr);
-      View dl1 = dx(pg, {{dl2, &pi.layers[2], 0}}, H, B, actP, dsrc_of(actP, ap1s, ap1zs));
-      dw(pg, pi.layers[2], dl2, {ap1s}, B, CNT_ADAM_PI, cfg.policy_lr);
-      const View ap0s = ap0.sub(0, B);
-      View gl0 = dx(pg, {{dl1, &pi.layers[1], 0}}, H, B, DxOpt().nb_defer(nbd ? &ap0s : nullptr).images(!nbd, nbd));
-      dw(pg, pi.layers[1], dl1, {ap0s, fzs}, B, CNT_ADAM_PI, cfg.policy_lr);
-      if (nbd) {
-        dw(pg, pi.layers[0], gl0, {s}, B, CNT_ADAM_PI, cfg.policy_lr, DwOpt().nb_defer(&ap0s));
-      } else {
-        View dl0 = normbwd(pg, gl0, ap0s);
-        dw(pg, pi.layers[0], dl0, {s}, B, CNT_ADAM_PI, cfg.policy_lr);
-      }
+  }
+  // Upper bound on the tiles of an EPI_QHEAD GEMM over B rows (its loss partial slots).
+  int qhead_tiles(const Layer& L) const { return cdiv(B, kTileM) * cdiv(L.out, kTileM); }
+  // Policy pass (td7.py:259-276) through the updated critics (no weight gradient of these layers), the actor's
+  // backward + Adam
+  void td7_policy(Prog& pg, StepBuild& sb, const Td7Actor& ac) {
+    Net& fe = net("fixed_encoder");
+    Net& pi = net("policy");
+    Net* q[2] = {&net("q1"), &net("q2")};
+    const Layer* qo[2] = {&q[0]->layers[3], &q[1]->layers[3]};
+    const View &s = sb.s, &a_pi = ac.a_pi, &fzs = ac.fzs;
+    const bool nbd = td7_nb_defer(), fold = td7_fold();
+    const FwdOpt fo = FwdOpt().no_t();
+    View pa1z, pa2z;
+    View pa1 = fwd(pg, fe.layers[3], {{fzs}, {a_pi}}, B, actE, FwdOpt(fo).keep_pre(&pa1z));
+    View pa2 = fwd(pg, fe.layers[4], {{pa1}}, B, actE, FwdOpt(fo).keep_pre(&pa2z));
+    View pzsa = fwd(pg, fe.layers[5], {{pa2}}, B, ACT_NONE, fo);
+    View p01[2], p1[2], p1z[2], dzp2[2];
+    for (int n = 0; n < 2; ++n) {
+      p01[n] = fwd(pg, q[n]->layers[0], {{s}, {a_pi}}, B, ACT_NONE, FwdOpt(fo).norm());
+      p1[n] = fwd(pg, q[n]->layers[1], {{p01[n]}, {pzsa}, {fzs}}, B, actC, FwdOpt(fo).keep_pre(&p1z[n]));
     }
-    // ---- step end: info row [encoder, q_fn, policy]
+    // q2 + q3 + dL/dQ = -1/(2B) fused (EPI_QHEAD): dZ of q2 straight from the GEMM (read by the input-gradient
+    // GEMM only: no weight update here).  One loss resource per critic: the two heads share a level
+    sb.ploss.id = next_id++;
+    sb.ploss_id2 = next_id++;
+    sb.ploss.p = mem.make<float>((size_t)(qhead_tiles(q[0]->layers[2]) + qhead_tiles(q[1]->layers[2])));
+    for (int n = 0; n < 2; ++n) {
+      LossPart slot{sb.ploss.p + sb.ploss.n, 0, n ? sb.ploss_id2 : sb.ploss.id};
+      dzp2[n] = fwd(pg, q[n]->layers[2], {{p1[n]}}, B, actC, FwdOpt(fo).q_head(qo[n], -0.5f / (float)Bv, &slot));
+      sb.ploss.n += slot.n;
+    }
+    // ---- offline (rle_config bc_lambda): + lmbda * mean|cat Q|.detach() * mse(pi(s), a).  dL/dq stays
+    // -1/(2B) (q_abs is detached), so the q-heads above are the online ones.  The per-row q for q_abs: the
+    // same layers once more with the EPI_QDOT epilogue, beside the q-heads (same level, nothing waits for
+    // them but OP_BC); OP_BC a level later forms q_abs, bc and e = dL_bc / d pi, which the action gradient
+    // below reads several levels on.
+    if (offline()) {
+      add_bc(pg, sb, 0, cfg.bc_lambda, &a_pi);
+      View pq[2];
+      for (int n = 0; n < 2; ++n) pq[n] = fwd(pg, q[n]->layers[2], {{p1[n]}}, B, actC, FwdOpt(fo).q_dot(qo[n]));
+      add_bc(pg, sb, 1, 0.f, pq, qo);
+    }
+    View dzp1[2], dxp01[2];
+    const DxOpt po = DxOpt().no_t();  // (no weight gradient of the critics or the fixed encoder in the policy pass)
+    for (int n = 0; n < 2; ++n) {
+      dzp1[n] = dx(pg, {{dzp2[n], &q[n]->layers[2], 0}}, H, B, actC, &p1z[n], po);
+      View g = dx(pg, {{dzp1[n], &q[n]->layers[1], 0}}, H, B, po);
+      dxp01[n] = normbwd(pg, g, p01[n], NormBwdOpt().no_t());
+    }
+    // grad wrt zsa from both critics (q1 input columns [H, 2H))
+    View dpa2;
+    if (fold) {  // d zsa -> d pa2 through zsa3 folded: G_n = q_n.q1[:, zsa block] x fe.zsa3 (updated critics)
+      View G[2];
+      for (int n = 0; n < 2; ++n)
+        G[n] = dx(pg, {{wview_n(q[n]->layers[1], Hp, H), &fe.layers[5], 0}}, H, H);  // (a T-image operand below)
+      dpa2 = dx(pg, {{dzp1[0], nullptr, 0, &G[0]}, {dzp1[1], nullptr, 0, &G[1]}}, H, B, actE, &pa2z, po);
+    } else {
+      View gzsa = dx(pg, {{dzp1[0], &q[0]->layers[1], Hp}, {dzp1[1], &q[1]->layers[1], Hp}}, Z, B);
+      dpa2 = dx(pg, {{gzsa, &fe.layers[5], 0}}, H, B, actE, &pa2z);
+    }
+    View dpa1 = dx(pg, {{dpa2, &fe.layers[4], 0}}, H, B, actE, &pa1z, po);
+    // d action = sum of three paths, then tanh' (actor output)
+    std::vector<DxTerm> t3{
+        {dxp01[0], &q[0]->layers[0], Sp}, {dxp01[1], &q[1]->layers[0], Sp}, {dpa1, &fe.layers[3], Zp}};
+    // (offline: e0 x (q_abs I), the behaviour-cloning gradient wrt pi, one more reduction segment ahead of
+    // tanh' -- in the in-tile recomputation below as well, so RLE_FUSE_PRE stays)
+    if (offline()) t3.push_back({sb.bc_e, nullptr, 0, &sb.bc_eye});
+    View dl3 = dx(pg, t3, A, B, ACT_TANH, &a_pi);
+    const PreUse p3 = ac.prea ? pre_actor_dx(t3, A, a_pi, 0) : PreUse{};  // dl2 recomputes dl3 in-tile
+    // input-grads through a layer are emitted BEFORE its Adam update so the
+    // scheduler orders them against the pre-update weights (as autograd does)
+    View ap2s = ac.ap2.sub(0, B), ap1s = ac.ap1.sub(0, B);
+    const View ap2zs = actP == ACT_ELU ? ac.ap2z.sub(0, B) : View{}, ap1zs = actP == ACT_ELU ? ac.ap1z.sub(0, B) : View{};
+    View dl2 = dx(pg, {{dl3, &pi.layers[3], 0}}, H, B, actP, dsrc_of(actP, ap2s, ap2zs),
+                  DxOpt().pre_gemm(ac.prea ? &p3 : nullptr));
+    dw(pg, pi.layers[3], dl3, {ap2s}, B, CNT_ADAM_PI, cfg.policy_lr);
+    View dl1 = dx(pg, {{dl2, &pi.layers[2], 0}}, H, B, actP, dsrc_of(actP, ap1s, ap1zs));
+    dw(pg, pi.layers[2], dl2, {ap1s}, B, CNT_ADAM_PI, cfg.policy_lr);
+    const View ap0s = ac.ap0.sub(0, B);
+    View gl0 = dx(pg, {{dl1, &pi.layers[1], 0}}, H, B, DxOpt().nb_defer(nbd ? &ap0s : nullptr).images(!nbd, nbd));
+    dw(pg, pi.layers[1], dl1, {ap0s, fzs}, B, CNT_ADAM_PI, cfg.policy_lr);
+    if (nbd) {
+      dw(pg, pi.layers[0], gl0, {s}, B, CNT_ADAM_PI, cfg.policy_lr, DwOpt().nb_defer(&ap0s));
+    } else {
+      View dl0 = normbwd(pg, gl0, ap0s);
+      dw(pg, pi.layers[0], dl0, {s}, B, CNT_ADAM_PI, cfg.policy_lr);
+    }
+  }
+  // Step end: info row [encoder, q_fn, policy] (offline: + [bc, q_abs])
+  void td7_step_end(Prog& pg, const StepBuild& sb) {
     Op op = step_end_op();
     StepEndArgs& a = op.end;
-    info_sum(a, 0, enc_loss, enc_tiles, 1, 1.f / (float)((long long)Bv * Z));
-    info_sum(a, 1, qloss_part, hw * 4, 1, (lap ? 1.f : 0.5f) / (float)Bv);
-    if (policy) info_sum(a, 2, ploss_part, ploss_n, 1, -0.5f / (float)Bv);
+    info_sum(a, 0, sb.enc_loss.p, sb.enc_loss.n, 1, 1.f / (float)((long long)Bv * Z));
+    info_sum(a, 1, sb.qloss.p, sb.qloss.n, 1, (cfg.use_lap ? 1.f : 0.5f) / (float)Bv);
+    if (sb.policy) info_sum(a, 2, sb.ploss.p, sb.ploss.n, 1, -0.5f / (float)Bv);
     else a.kind[2] = INFO_NAN;
     a.ninfo = 3;
-    std::vector<int> rd{loss_id_enc, qloss_id};
-    if (policy) {
-      rd.push_back(ploss_id);
-      rd.push_back(ploss_id2);
-    }
-    if (offline()) {  // info row [encoder, q_fn, policy, bc, q_abs]
-      a.ninfo = 5;
-      if (policy) {
-        a.kind[2] = INFO_SUM_BC;
-        a.bcs = bc_s;
-        a.bc_lambda = cfg.bc_lambda;
-        info_sum(a, 3, bc_part, bc_part_n, 1, 1.f / ((float)Bv * (float)A));
-        info_sum(a, 4, bc_s, 1, 1, 1.f);
-        rd.push_back(bc_s_id);
-        rd.push_back(bc_part_id);
-      } else {
-        a.kind[3] = a.kind[4] = INFO_NAN;
-      }
-    }
+    std::vector<int> rd{sb.enc_loss.id, sb.qloss.id};
+    if (sb.policy) rd.insert(rd.end(), {sb.ploss.id, sb.ploss_id2});
+    if (offline()) info_offline(a, rd, sb);
     std::vector<int> cn{CNT_ADAM_Q, CNT_ADAM_ENC, 3, CNT_RNG, CNT_TAPE};
-    if (policy) cn.push_back(CNT_ADAM_PI);
+    if (sb.policy) cn.push_back(CNT_ADAM_PI);
     add_step_end(pg, op, rd, cn);
   }
-  int loss_id_enc = -1, qloss_id = -1, ploss_id = -1, ploss_id2 = -1, ploss_n = 0;
-  // TD7 offline mode (rle_config bc_lambda > 0): OP_BC's outputs of the program being built -- q_abs, and the
-  // row blocks' sums of (pi - a)^2
-  bool offline() const { return algo == RLE_TD7 && cfg.bc_lambda > 0.f; }
-  // Offline TD3 (rle_config_ext bc_alpha > 0, TD3+BC): the same outputs, bc_s = {q_abs, lmbda}
-  float bc_alpha = 0.f;
-  bool offline3() const { return algo == RLE_TD3 && bc_alpha > 0.f; }
-  float* bc_s = nullptr;
-  float* bc_part = nullptr;
-  int bc_s_id = -1, bc_part_id = -1, bc_part_n = 0;
-
-  // Upper bound on the tiles of a fwd_qhead GEMM over B rows (its loss partial slots).
-  int qhead_tiles(const Layer& L) const { return cdiv(B, kTileM) * cdiv(L.out, kTileM); }
-  // dZ of a critic's last hidden layer L (input x, activation ELU) under a constant dL/dq
-  // through the head layer Lq (H -> 1), and per-tile sums of Q - b3 (+ B b3 on tile 0)
-  // into part[0, *ntiles).
-  View fwd_qhead(Prog& pg, const Layer& L, const Layer& Lq, const View& x, int M, float dq, float* part,
-                 int* ntiles, int loss_id) {
-    REQUIRE(L.seg_p.size() == 1 && x.cols == L.seg_p[0] && x.m.n && Lq.out == 1, "qhead: operand layout");
-    Op op{};
-    op.kind = OP_GEMM;
-    GemmArgs& g = op.gemm;
-    g.mode = GEMM_FWD;
-    g.A.seg[0] = seg_n(x, 0, L.K);
-    g.A.nseg = 1;
-    Seg w{};
-    w.p = P + L.wn_off;
-    w.xs = L.cb;
-    w.x1 = L.out;
-    w.r1 = L.K;
-    g.B.seg[0] = w;
-    g.B.nseg = 1;
-    g.M = M;
-    g.N = L.out;
-    g.R = L.K;
-    const auto tq = choose_tn(M, L.out);
-    const bool wide = plan.wide && M % 64 == 0 && L.out % plan.wide == 0;
-    g.tn = wide ? plan.wide : tq.first;
-    g.hot.wide = wide ? plan.wide : 0;
-    op.seq = tq.second;
-    g.tiles_m = cdiv(M, kTileM);
-    g.tiles_n = cdiv(L.out, g.tn);
-    *ntiles = g.tiles_m * g.tiles_n;  // (wide: one loss partial per 16-row block too)
-    g.epi = EPI_QHEAD;
-    g.act = actC;
-    g.bias = bias(L);
-    View dz = buf(M, L.out, true, false);  // (read by the input-gradient GEMM only: no weight update here)
-    g.out = dz.m;
-    g.loss_part = part;
-    g.qw = P + Lq.wn_off;
-    g.qw_cbn = Lq.cb;
-    g.qb = bias(Lq);
-    g.qscale = dq;
-    g.mvalid = Bv;
-    op.wg_count = (wide ? g.tiles_m / 4 : g.tiles_m) * g.tiles_n;
-    pg.add(op, {x.id, L.res, Lq.res}, {dz.id, loss_id});
-    return dz;
+  void build_td7(Prog& pg, bool policy, int set) {
+    StepBuild sb = begin_step(pg, policy, set);
+    td7_encoder_update(pg, sb);
+    const Td7Actor ac = td7_fixed_and_actor(pg, sb);
+    const TwinViews th = td7_target(pg, sb, ac);
+    const Td7Critics cr = td7_critics(pg, sb, ac, th);
+    td7_critic_backward(pg, sb, ac, cr);
+    if (policy) td7_policy(pg, sb, ac);
+    td7_step_end(pg, sb);
   }
-  float* qloss_part = nullptr;
-  float* ploss_part = nullptr;
+
 
   // Algebraic folds of TD7's linear zsa3 layer into its consumers (build_td7): on when
   // every block is 16-aligned and zs_dim = hdim (the folded block replaces the zsa block in place).
@@ -4027,23 +4074,25 @@ struct Engine {
     return alpha_fixed;
   }
 
-  // TD3 (td3.py:206-242) and SAC (sac.py:251-295)
-  void build_mlp(Prog& pg, bool policy, int set) {
+  // ---- TD3 (td3.py:206-242) and SAC (sac.py:251-295): build_mlp below is the list of these phases.
+  // Actor on [s; s'] (the target policy aliases the policy, Q1; SAC's policy is unchanged until its step) with
+  // the TD3 (tanh + target smoothing noise) or the SAC (rsample) head.  The later phases read:
+  struct MlpActor {
+    std::vector<View> h, hz;  // the hidden layers' outputs on [s; s'] (hz: an ELU actor's pre-activations)
+    View raw, logpi;          // SAC: the raw head (mean | log_std) and log pi of the sampled actions
+    View a_pi, a_next;        // the action on s; on s' (behind a pre-GEMM: layout only)
+    bool prea = false;        // TD3: the target critics' first layer recomputes a' in-tile (pre-GEMM, as TD7)
+    PreUse pn1, psac;         // that pre-GEMM; SAC's, from the raw head (has_pre 5)
+    const PreUse* tpre() const { return prea ? &pn1 : (psac.kind == 5 ? &psac : nullptr); }
+  };
+  MlpActor mlp_actor(Prog& pg) {
     const bool sac = algo == RLE_SAC;
-    const int B2 = 2 * B;
+    const int B2 = 2 * B, D = (int)HS.size();  // make_mlp's depth (mlp.py:24-35): D hidden layers, then Lout
     Net& pi = net("policy");
-    Net* q[2] = {&net("q1"), &net("q2")};
-    Net* tq[2] = {&net("target_q1"), &net("target_q2")};
-    const bool lap = cfg.use_lap && !sac;
-    use_set(set);
-    asc_set = set;
-    add_adam_scalars(pg);
-    View s = ss.sub(0, B), s2 = ss.sub(B, B);
-    // make_mlp's depth (mlp.py:24-35): D hidden layers, then the output layer Lout
-    const int D = (int)HS.size();
     const Layer& Lout = pi.layers[D];
-    // actor on [s; s'] (target policy aliases the policy, Q1; SAC policy unchanged until its step)
-    std::vector<View> h(D), hz(D);  // (hz: an ELU actor's pre-activations, for the policy backward)
+    MlpActor o;
+    std::vector<View>&h = o.h, &hz = o.hz;
+    h.resize(D), hz.resize(D);
     const bool pz = actP == ACT_ELU;
     const bool pl01 = prelayer_ok(pi.layers[0], pi.layers[1]);  // (the second layer recomputes the first in-tile)
     h[0] = fwd(pg, pi.layers[0], {{ss}}, B2, actP, FwdOpt().keep_pre(pz ? &hz[0] : nullptr).pl_source(pl01));
@@ -4052,23 +4101,22 @@ struct Engine {
       h[i] = fwd(pg, pi.layers[i], {{h[i - 1]}}, B2, actP,
                  FwdOpt().keep_pre(pz ? &hz[i] : nullptr).pre_gemm(i == 1 && pl0.kind == 3 ? &pl0 : nullptr));
     const View hl = h[D - 1];  // the last hidden layer's output
-    View actv, raw, logpi;
-    // TD3: the target critics' first layer recomputes a' in-tile (pre-GEMM, as TD7)
-    const bool prea = !sac && actor_pre();
+    View actv;
+    o.prea = !sac && actor_pre();
     const View h1n = hl.sub(B, B);
-    const PreUse pn1 = prea ? pre_actor_fwd(Lout, h1n, &eps, 1) : PreUse{};
+    if (o.prea) o.pn1 = pre_actor_fwd(Lout, h1n, &eps, 1);
     if (!sac) {
-      actv = prea ? fwd(pg, Lout, {{hl.sub(0, B)}}, B, ACT_TANH)
-                  : fwd(pg, Lout, {{hl}}, B2, ACT_TANH, FwdOpt().noised(&eps, B));
+      actv = o.prea ? fwd(pg, Lout, {{hl.sub(0, B)}}, B, ACT_TANH)
+                    : fwd(pg, Lout, {{hl}}, B2, ACT_TANH, FwdOpt().noised(&eps, B));
     } else if (sac_fwd_fused()) {  // the rsample in the raw head's epilogue (one level fewer)
       actv = buf(B2, A);
-      logpi = vec(B2);
+      o.logpi = vec(B2);
       SacFwdUse sfu{};
       SacFwdArgs& a = sfu.a;
       a.eps = eps.m;
       a.eps2 = eps2.m;
       a.act = actv.m;
-      a.logpi = logpi.p;
+      a.logpi = o.logpi.p;
       a.min_log_std = cfg.min_log_std;
       a.max_log_std = cfg.max_log_std;
       a.A = A;
@@ -4076,372 +4124,285 @@ struct Engine {
       a.ls_off = A;
       a.eps_row_split = B;
       sfu.rd = {eps.id, eps2.id};
-      sfu.wr = {actv.id, logpi.id};
-      raw = fwd(pg, Lout, {{hl}}, B2, ACT_NONE, FwdOpt().sac_fwd(&sfu));
+      sfu.wr = {actv.id, o.logpi.id};
+      o.raw = fwd(pg, Lout, {{hl}}, B2, ACT_NONE, FwdOpt().sac_fwd(&sfu));
     } else {
-      raw = fwd(pg, Lout, {{hl}}, B2, ACT_NONE);
+      o.raw = fwd(pg, Lout, {{hl}}, B2, ACT_NONE);
       actv = buf(B2, A);
-      logpi = vec(B2);
-      Op op = sac_actor_op(OP_SAC_ACTOR, raw.m, B2);
+      o.logpi = vec(B2);
+      Op op = sac_actor_op(OP_SAC_ACTOR, o.raw.m, B2);
       SacActorArgs& a = op.sac;
       a.eps = eps.m;
       a.eps2 = eps2.m;
       a.eps_row_split = B;
       a.act = actv.m;
-      a.logpi = logpi.p;
-      pg.add(op, {raw.id, eps.id, eps2.id}, {actv.id, logpi.id});
+      a.logpi = o.logpi.p;
+      pg.add(op, {o.raw.id, eps.id, eps2.id}, {actv.id, o.logpi.id});
     }
-    View a_pi = actv.sub(0, B), a_next = prea ? a_pi : actv.sub(B, B);  // (pre: layout only)
-    // SAC: the target critics' first layer recomputes a' in-tile from the raw head (pre-GEMM, has_pre 5)
-    const PreUse psac = sac && sac_pre() ? pre_sac_fwd(Lout, h1n, eps, 1) : PreUse{};
-    const PreUse* tpre = prea ? &pn1 : (psac.kind == 5 ? &psac : nullptr);
-    // target critics + y
+    o.a_pi = actv.sub(0, B);
+    o.a_next = o.prea ? o.a_pi : actv.sub(B, B);
+    if (sac && sac_pre()) o.psac = pre_sac_fwd(Lout, h1n, eps, 1);
+    return o;
+  }
+  // Target critics (forward only) and y, the online critics and the loss head (td3.py:160-164, sac.py:188-193:
+  // y per row, then the loss), the priority update and the next step's batch.  The backward reads:
+  struct MlpCritics {
+    std::vector<View> c[2], cz[2];  // the hidden layers' outputs and (ELU critics) pre-activations
+    View dz1[2], dq[2];             // the head's gradients: dZ of the last hidden layer, dq
+    bool hdx = false;               // the head ran inside the DX of each critic's last hidden layer, ...
+    View d0f[2];                    // ... which gave dZ of the layer before
+  };
+  MlpCritics mlp_critics(Prog& pg, StepBuild& sb, const MlpActor& ac) {
+    const bool sac = algo == RLE_SAC;
+    const int D = (int)HS.size();
+    Net* q[2] = {&net("q1"), &net("q2")};
+    Net* tq[2] = {&net("target_q1"), &net("target_q2")};
+    const bool lap = cfg.use_lap && !sac;
+    MlpCritics o;
     std::vector<View> th[2];
-    const bool hdx = mlp_headdx();
+    o.hdx = mlp_headdx();
     for (int n = 0; n < 2; ++n)  // (forward only)
-      mlp_critic_fwd(pg, *tq[n], s2, a_next, th[n], /*out_t*/ false, tpre, true, hdx);
-    // online critics
-    std::vector<View> c[2], cz[2];
-    for (int n = 0; n < 2; ++n) mlp_critic_fwd(pg, *q[n], s, act_in, c[n], /*out_t*/ true, nullptr, true, hdx, &cz[n]);
-    // (the loss heads' derivative rows: ELU' reads the pre-activation; ReLU' / identity the output)
+      mlp_critic_fwd(pg, *tq[n], sb.s2, ac.a_next, th[n], /*out_t*/ false, ac.tpre(), true, o.hdx);
+    for (int n = 0; n < 2; ++n)
+      mlp_critic_fwd(pg, *q[n], sb.s, act_in, o.c[n], /*out_t*/ true, nullptr, true, o.hdx, &o.cz[n]);
+    // (the loss head's derivative rows: ELU' reads the pre-activation; ReLU' / identity the output)
     const bool cze = actC == ACT_ELU;
     // (the last hidden layers and the heads' layers)
-    const View c1[2] = {c[0][D - 1], c[1][D - 1]}, th1[2] = {th[0][D - 1], th[1][D - 1]};
+    const View c1[2] = {o.c[0][D - 1], o.c[1][D - 1]}, th1[2] = {th[0][D - 1], th[1][D - 1]};
+    const View cz1[2] = {o.cz[0][D - 1], o.cz[1][D - 1]};
     const Layer *qo[2] = {&q[0]->layers[D], &q[1]->layers[D]}, *tqo[2] = {&tq[0]->layers[D], &tq[1]->layers[D]};
-    // (dZ of the critics' last hidden layers: with the fused head only their weight gradients read
-    // it, in the T image)
-    View dz1[2] = {buf(B, H, !hdx, true), buf(B, H, !hdx, true)},
-         dq[2] = {buf(B, 1, false, true), buf(B, 1, false, true)};
-    View d0f[2];  // (hdx) dZ of each critic's first hidden layer from the fused head + DX
-    View prio = vec(B);
-    const int hw = cdiv(B, 4);
-    qloss_part = mem.make<float>((size_t)hw * 4);
-    {
-      // target head (td3.py:160-164, sac.py:188-193) fused: y per row, then the loss
-      Op op = head_op(HEAD_MLP_LOSS, Bv);
-      HeadArgs& h = op.head;
-      set_head_twin(h, c1[0], c1[1], *qo[0], *qo[1]);
-      set_head_target(h, HEAD_MLP_TARGET, th1[0], th1[1], *tqo[0], *tqo[1]);
-      h.reward = rw.p;
-      h.notdone = nd.p;
-      std::vector<int> rd{c1[0].id, c1[1].id, qo[0]->res, qo[1]->res, th1[0].id, th1[1].id,
-                          tqo[0]->res, tqo[1]->res, rw.id, nd.id};
-      if (sac) {
-        h.sac = 1;
-        h.logpi = logpi.p + B;  // next-state rows
-        h.log_alpha = alpha_src();
-        h.alpha_lin = cfg.tmp >= 0.f;
-        rd.push_back(logpi.id);
-        rd.push_back(R_LA);
-      }
-      h.dsrc[0] = (cze ? cz[0][D - 1] : c1[0]).m;
-      h.dsrc[1] = (cze ? cz[1][D - 1] : c1[1]).m;
-      if (cze) rd.insert(rd.end(), {cz[0][D - 1].id, cz[1][D - 1].id});
-      h.dact = actC;
-      h.lap = lap;
-      h.dz[0] = dz1[0].m;
-      h.dz[1] = dz1[1].m;
-      h.dq[0] = dq[0].m;
-      h.dq[1] = dq[1].m;
-      h.loss_part = qloss_part;
-      h.prio = prio.p;
-      qloss_id = next_id++;
-      if (!hdx) {
-        pg.add(op, rd, {dz1[0].id, dz1[1].id, dq[0].id, dq[1].id, prio.id, qloss_id});
-      } else {
-        // the head runs inside the DX of each critic's last hidden layer; critic 0's op stores the
-        // priorities and loss partials
-        set_head_parts(h, c1, th1, rd);
-        for (int n = 0; n < 2; ++n) {
-          HeadUse hu{h, n, rd, {dz1[n].id, dq[n].id}};
-          if (n == 0) hu.wr.insert(hu.wr.end(), {prio.id, qloss_id});
-          // (the head forms dZ = dq w act'(segment 0): an ELU critic's pre-activations, a ReLU critic's outputs)
-          d0f[n] = dx(pg, {{cze ? cz[n][D - 1] : c1[n], &q[n]->layers[D - 1], 0}}, HS[D - 2], B, actC,
-                      dsrc_of(actC, c[n][D - 2], cz[n][D - 2]), DxOpt().head_use(&hu));
-        }
+    LossHead lh = loss_head(sb, HEAD_MLP_LOSS, HEAD_MLP_TARGET, c1, cze ? cz1 : c1, th1, qo, tqo, o.hdx, lap);
+    HeadArgs& h = lh.op.head;
+    if (sac) set_head_sac(h, ac.logpi, B, lh.rd);  // (the next-state rows)
+    if (cze) lh.rd.insert(lh.rd.end(), {cz1[0].id, cz1[1].id});
+    for (int n = 0; n < 2; ++n) o.dz1[n] = lh.dz[n], o.dq[n] = lh.dq[n];
+    if (!o.hdx) {
+      pg.add(lh.op, lh.rd, {lh.dz[0].id, lh.dz[1].id, lh.dq[0].id, lh.dq[1].id, lh.prio.id, sb.qloss.id});
+    } else {
+      // the head runs inside the DX of each critic's last hidden layer; critic 0's op stores the
+      // priorities and loss partials
+      set_head_parts(h, c1, th1, lh.rd);
+      for (int n = 0; n < 2; ++n) {
+        HeadUse hu{h, n, lh.rd, {lh.dz[n].id, lh.dq[n].id}};
+        if (n == 0) hu.wr.insert(hu.wr.end(), {lh.prio.id, sb.qloss.id});
+        // (the head forms dZ = dq w act'(segment 0): an ELU critic's pre-activations, a ReLU critic's outputs)
+        o.d0f[n] = dx(pg, {{cze ? cz1[n] : c1[n], &q[n]->layers[D - 1], 0}}, HS[D - 2], B, actC,
+                      dsrc_of(actC, o.c[n][D - 2], o.cz[n][D - 2]), DxOpt().head_use(&hu));
       }
     }
-    add_update_and_prefetch(pg, sac, set, lap, prio);
-    for (int n = 0; n < 2; ++n) {  // (input gradients through a layer before its Adam update)
-      Net& Q = *q[n];
-      dw(pg, Q.layers[D], dq[n], {c1[n]}, B, CNT_ADAM_Q, cfg.critic_lr);
-      View d = dz1[n];  // dZ of hidden layer i, from i = D - 1 down
+    add_update_and_prefetch(pg, sac, sb.set, lap, lh.prio);
+    return o;
+  }
+  // Critic backward + Adam (input gradients through a layer before its Adam update)
+  void mlp_critic_backward(Prog& pg, const StepBuild& sb, const MlpCritics& cr) {
+    const int D = (int)HS.size();
+    for (int n = 0; n < 2; ++n) {
+      Net& Q = net(n ? "q2" : "q1");
+      dw(pg, Q.layers[D], cr.dq[n], {cr.c[n][D - 1]}, B, CNT_ADAM_Q, cfg.critic_lr);
+      View d = cr.dz1[n];  // dZ of hidden layer i, from i = D - 1 down
       for (int i = D - 1; i >= 1; --i) {
-        const View dp = hdx && i == D - 1 ? d0f[n]
-                                           : dx(pg, {{d, &Q.layers[i], 0}}, HS[i - 1], B, actC,
-                                                dsrc_of(actC, c[n][i - 1], cz[n][i - 1]));
-        dw(pg, Q.layers[i], d, {c[n][i - 1]}, B, CNT_ADAM_Q, cfg.critic_lr);
+        const View dp = cr.hdx && i == D - 1 ? cr.d0f[n]
+                                              : dx(pg, {{d, &Q.layers[i], 0}}, HS[i - 1], B, actC,
+                                                   dsrc_of(actC, cr.c[n][i - 1], cr.cz[n][i - 1]));
+        dw(pg, Q.layers[i], d, {cr.c[n][i - 1]}, B, CNT_ADAM_Q, cfg.critic_lr);
         d = dp;
       }
-      dw(pg, Q.layers[0], d, {s, act_in}, B, CNT_ADAM_Q, cfg.critic_lr);
+      dw(pg, Q.layers[0], d, {sb.s, act_in}, B, CNT_ADAM_Q, cfg.critic_lr);
     }
-    ploss_part = nullptr;
-    float* gsq = nullptr;
-    int ngsq = 0;
-    if (policy) {
-      std::vector<View> pc[2], pcz[2];
+  }
+  // Policy pass through the updated critics, the objective's head, the actor's backward + Adam
+  void mlp_policy(Prog& pg, StepBuild& sb, const MlpActor& ac) {
+    const bool sac = algo == RLE_SAC;
+    const int D = (int)HS.size();
+    Net& pi = net("policy");
+    Net* q[2] = {&net("q1"), &net("q2")};
+    const Layer& Lout = pi.layers[D];
+    const Layer* qo[2] = {&q[0]->layers[D], &q[1]->layers[D]};
+    const View &s = sb.s, &a_pi = ac.a_pi, &raw = ac.raw;
+    const bool hdx = mlp_headdx(), cze = actC == ACT_ELU, pz = actP == ACT_ELU;
+    std::vector<View> pc[2], pcz[2];
+    for (int n = 0; n < 2; ++n)
+      mlp_critic_fwd(pg, *q[n], s, a_pi, pc[n], /*out_t*/ true, nullptr, /*last_t*/ false, hdx, &pcz[n]);
+    const View p1[2] = {pc[0][D - 1], pc[1][D - 1]};
+    // (no weight gradient of the critics in the policy pass: the gradients keep N images only)
+    const DxOpt po = DxOpt().no_t();
+    View dzp1[2];
+    if (!hdx) dzp1[0] = buf(B, H, true, false), dzp1[1] = buf(B, H, true, false);
+    sb.ploss.n = cdiv(B, 4);  // (4 partials per head workgroup)
+    sb.ploss.p = mem.make<float>((size_t)sb.ploss.n * 4);
+    // the objective's head: inside the DX of each critic's last hidden layer (hdx: critic 0's op stores the loss
+    // partials), or standalone, forming dZ of the last hidden layers (dzp1) itself
+    Op op = head_op(HEAD_MLP_POLICY, Bv);
+    HeadArgs& h = op.head;
+    set_head_twin(h, p1[0], p1[1], *qo[0], *qo[1]);
+    h.dact = actC;
+    h.loss_part = sb.ploss.p;
+    std::vector<int> rd{p1[0].id, p1[1].id, qo[0]->res, qo[1]->res};
+    if (!hdx) {
+      for (int n = 0; n < 2; ++n) {
+        h.dsrc[n] = (cze ? pcz[n][D - 1] : p1[n]).m;
+        h.dz[n] = dzp1[n].m;
+      }
+      if (cze) rd.insert(rd.end(), {pcz[0][D - 1].id, pcz[1][D - 1].id});
+    }
+    if (sac) set_head_sac(h, ac.logpi, 0, rd);
+    if (hdx) set_head_parts(h, p1, nullptr, rd);
+    sb.ploss.id = next_id++;
+    if (!hdx) pg.add(op, rd, {dzp1[0].id, dzp1[1].id, sb.ploss.id});
+    View dzp0[2];
+    for (int n = 0; n < 2; ++n) {
+      HeadUse hu{h, n, rd, {}};
+      if (n == 0) hu.wr.push_back(sb.ploss.id);
+      // (the fused head forms dZ = dq w act'(segment 0), as the loss head's)
+      const View& z = hdx ? (cze ? pcz[n][D - 1] : p1[n]) : dzp1[n];
+      dzp0[n] = dx(pg, {{z, &q[n]->layers[D - 1], 0}}, HS[D - 2], B, actC, dsrc_of(actC, pc[n][D - 2], pcz[n][D - 2]),
+                   DxOpt(po).head_use(hdx ? &hu : nullptr));
+    }
+    // ---- offline (rle_config_ext bc_alpha): L = -lmbda mean(min Q) + mse(pi(s), a), lmbda = bc_alpha /
+    // mean|min Q| (detached).  Scale at the end: the chain above and below stays the online one (dL/dq = -1/B),
+    // so it carries the gradient of L / lmbda; the cloning term enters the action gradient as e0 x (q_abs /
+    // bc_alpha) I (one more reduction segment ahead of tanh', TD7's construction), and the actor's Adam
+    // epilogues multiply by lmbda.  OP_BC mode 0 needs the actor output alone (many levels earlier); q_abs
+    // comes from the policy pass's row partials beside the fused head (mode 3) or from the standalone head's
+    // |min| partials a level after it (mode 2): either way it is ready a level before the action gradient.
+    if (offline3()) {
+      add_bc(pg, sb, 0, 1.f, &a_pi);
+      add_bc(pg, sb, hdx ? 3 : 2, bc_alpha, p1, qo);
+    }
+    // (deeper critics: on down to the first hidden layer; no weight gradient reads these)
+    for (int i = D - 2; i >= 1; --i)
       for (int n = 0; n < 2; ++n)
-        mlp_critic_fwd(pg, *q[n], s, a_pi, pc[n], /*out_t*/ true, nullptr, /*last_t*/ false, hdx, &pcz[n]);
-      const View p1[2] = {pc[0][D - 1], pc[1][D - 1]};
-      // (no weight gradient of the critics in the policy pass: the gradients keep N images only)
-      const DxOpt po = DxOpt().no_t();
-      View dzp1[2];
-      if (!hdx) dzp1[0] = buf(B, H, true, false), dzp1[1] = buf(B, H, true, false);
-      ploss_part = mem.make<float>((size_t)hw * 4);
-      View dzp0[2];
-      if (hdx) {  // the objective's head inside the DX of each critic's last hidden layer
-        Op op = head_op(HEAD_MLP_POLICY, Bv);
-        HeadArgs& h = op.head;
-        set_head_twin(h, p1[0], p1[1], *qo[0], *qo[1]);
-        h.dact = actC;
-        h.loss_part = ploss_part;
-        std::vector<int> rd{p1[0].id, p1[1].id, qo[0]->res, qo[1]->res};
-        if (sac) {
-          h.sac = 1;
-          h.logpi = logpi.p;
-          h.log_alpha = alpha_src();
-          h.alpha_lin = cfg.tmp >= 0.f;
-          rd.push_back(logpi.id);
-          rd.push_back(R_LA);
-        }
-        set_head_parts(h, p1, nullptr, rd);
-        ploss_id = next_id++;
-        for (int n = 0; n < 2; ++n) {
-          HeadUse hu{h, n, rd, {}};
-          if (n == 0) hu.wr.push_back(ploss_id);
-          dzp0[n] = dx(pg, {{cze ? pcz[n][D - 1] : p1[n], &q[n]->layers[D - 1], 0}}, HS[D - 2], B, actC,
-                       dsrc_of(actC, pc[n][D - 2], pcz[n][D - 2]), DxOpt(po).head_use(&hu));
-        }
-      } else {
-        Op op = head_op(HEAD_MLP_POLICY, Bv);
-        HeadArgs& h = op.head;
-        set_head_twin(h, p1[0], p1[1], *qo[0], *qo[1]);
-        h.dsrc[0] = (cze ? pcz[0][D - 1] : p1[0]).m;
-        h.dsrc[1] = (cze ? pcz[1][D - 1] : p1[1]).m;
-        h.dact = actC;
-        h.dz[0] = dzp1[0].m;
-        h.dz[1] = dzp1[1].m;
-        h.loss_part = ploss_part;
-        std::vector<int> rd{p1[0].id, p1[1].id, qo[0]->res, qo[1]->res};
-        if (cze) rd.insert(rd.end(), {pcz[0][D - 1].id, pcz[1][D - 1].id});
-        if (sac) {
-          h.sac = 1;
-          h.logpi = logpi.p;
-          h.log_alpha = alpha_src();
-          h.alpha_lin = cfg.tmp >= 0.f;
-          rd.push_back(logpi.id);
-          rd.push_back(R_LA);
-        }
-        pg.add(op, rd, {dzp1[0].id, dzp1[1].id, ploss_id = next_id++});
-        for (int n = 0; n < 2; ++n)
-          dzp0[n] = dx(pg, {{dzp1[n], &q[n]->layers[D - 1], 0}}, HS[D - 2], B, actC,
-                       dsrc_of(actC, pc[n][D - 2], pcz[n][D - 2]), po);
-      }
-      // ---- offline (rle_config_ext bc_alpha): L = -lmbda mean(min Q) + mse(pi(s), a), lmbda = bc_alpha /
-      // mean|min Q| (detached).  Scale at the end: the chain above and below stays the online one (dL/dq = -1/B),
-      // so it carries the gradient of L / lmbda; the cloning term enters the action gradient as e0 x (q_abs /
-      // bc_alpha) I (one more reduction segment ahead of tanh', TD7's construction), and the actor's Adam
-      // epilogues multiply by lmbda.  OP_BC mode 0 needs the actor output alone (many levels earlier); q_abs
-      // comes from the policy pass's row partials beside the fused head (mode 3) or from the standalone head's
-      // |min| partials a level after it (mode 2): either way it is ready a level before the action gradient.
-      View bc_e, bc_eye;
-      bc_s = nullptr;
-      if (offline3()) {
-        REQUIRE(A <= kThreads && a_pi.m.n && act_in.m.n, "bc: operand layout");
-        bc_e = buf(B, A, true, false);
-        bc_part_n = cdiv(Bv, 16);
-        bc_part = mem.make<float>((size_t)bc_part_n);
-        bc_part_id = next_id++;
-        {
-          Op op{};
-          op.kind = OP_BC;
-          BcArgs& b = op.bc;
-          b.mode = 0;
-          b.nvalid = Bv;
-          b.A = A;
-          b.lambda = 1.f;
-          b.pi = a_pi.m;
-          b.a = act_in.m;
-          b.e = bc_e.m;
-          b.part = bc_part;
-          op.wg_count = bc_part_n;
-          pg.add(op, {a_pi.id, act_in.id}, {bc_e.id, bc_part_id});
-        }
-        bc_eye = buf(A, A, false, true);
-        bc_s = mem.make<float>(4);
-        bc_s_id = next_id++;
-        Op op{};
-        op.kind = OP_BC;
-        BcArgs& b = op.bc;
-        b.lambda = bc_alpha;
-        b.nvalid = Bv;
-        b.A = A;
-        b.eye = bc_eye.m;
-        b.out = bc_s;
-        op.wg_count = 1;
-        if (hdx) {  // (the row partials the fused head reads: this op sits beside it, no level gained)
-          b.mode = 3;
-          for (int n = 0; n < 2; ++n) {
-            b.qp[n] = p1[n].qd;
-            b.qp_n[n] = p1[n].qd_n;
-            b.qb[n] = bias(*qo[n]);
-          }
-          REQUIRE(p1[0].qd && p1[1].qd && p1[0].qd_ld == p1[1].qd_ld, "bc: q partial layout");
-          b.qp_ld = p1[0].qd_ld;
-          pg.add(op, {p1[0].qd_id, p1[1].qd_id, qo[0]->res, qo[1]->res}, {bc_eye.id, bc_s_id});
-        } else {  // (the standalone head's |min| partials, a level after it and a level before the action gradient)
-          b.mode = 2;
-          b.qp[0] = ploss_part + 1;
-          b.qp_n[0] = hw;
-          b.qp_ld = 4;
-          pg.add(op, {ploss_id}, {bc_eye.id, bc_s_id});
-        }
-      }
-      // (deeper critics: on down to the first hidden layer; no weight gradient reads these)
-      for (int i = D - 2; i >= 1; --i)
-        for (int n = 0; n < 2; ++n)
-          dzp0[n] = dx(pg, {{dzp0[n], &q[n]->layers[i], 0}}, HS[i - 1], B, actC,
-                       dsrc_of(actC, pc[n][i - 1], pcz[n][i - 1]), po);
-      View dout;
-      PreUse pdout{};  // TD3: d1 recomputes dout in-tile
-      if (!sac) {
-        std::vector<DxTerm> ta{{dzp0[0], &q[0]->layers[0], Sp}, {dzp0[1], &q[1]->layers[0], Sp}};
-        // (offline: the cloning gradient, in the in-tile recomputation as well, so RLE_FUSE_PRE stays)
-        if (offline3()) ta.push_back({bc_e, nullptr, 0, &bc_eye});
-        dout = dx(pg, ta, A, B, ACT_TANH, &a_pi);
-        if (prea) pdout = pre_actor_dx(ta, A, a_pi, 0);
-      } else {
-        dout = buf(B, 2 * A);
-        if (sac_bwd_fused()) {  // the backward in the epilogue of the DX that forms da (one level fewer)
-          SacBwdUse sbu{};
-          SacBwdArgs& a = sbu.a;
-          a.raw = raw.m;
-          a.eps2 = eps2.m;
-          a.dout = dout.m;
-          a.log_alpha = alpha_src();
-          a.alpha_lin = cfg.tmp >= 0.f;
-          a.inv_b = 1.f / (float)Bv;
-          a.nvalid = Bv;
-          a.min_log_std = cfg.min_log_std;
-          a.max_log_std = cfg.max_log_std;
-          a.mean_off = 0;
-          a.ls_off = A;
-          sbu.rd = {raw.id, eps2.id, R_LA};
-          sbu.wr = {dout.id};
-          dx(pg, {{dzp0[0], &q[0]->layers[0], Sp}, {dzp0[1], &q[1]->layers[0], Sp}}, A, B, DxOpt().sac_bwd(&sbu));
-        }
-      }
-      if (sac && !sac_bwd_fused()) {
-        View da = dx(pg, {{dzp0[0], &q[0]->layers[0], Sp}, {dzp0[1], &q[1]->layers[0], Sp}}, A, B);
-        Op op = sac_actor_op(OP_SAC_ACTOR_BWD, raw.m, Bv);  // (rows of the padded batch past Bv keep a zero gradient)
-        SacActorArgs& a = op.sac;
-        a.eps2 = eps2.m;
-        a.da = da.m;
-        a.dout = dout.m;
-        a.log_alpha = alpha_src();
-        a.alpha_lin = cfg.tmp >= 0.f;
-        a.inv_b = 1.f / (float)Bv;
-        pg.add(op, {raw.id, eps2.id, da.id, R_LA}, {dout.id});
-      }
-      if (!sac) {
-        // per-tile grad-square partials for norm/policy (rl/nn/utils.py:13-19)
-        for (auto& L : pi.layers) ngsq += dw_gsq_w(L) + dw_gsq_b(L);
-        gsq = mem.make<float>(ngsq);
-      }
-      std::vector<int> tens;
-      float* gp = gsq;
-      auto gsq_for = [&](const Layer& L, int t_w, int t_b) -> std::pair<float*, float*> {
-        if (!gsq) return {nullptr, nullptr};
-        int nw = dw_gsq_w(L), nb = dw_gsq_b(L);
-        float* w = gp;
-        float* b = gp + nw;
-        gp += nw + nb;
-        for (int i = 0; i < nw; ++i) tens.push_back(t_w);
-        for (int i = 0; i < nb; ++i) tens.push_back(t_b);
-        return {w, b};
-      };
-      // actor backward: tensors in parameters() order mlp.0.w, mlp.0.b, mlp.2.w, ...
-      std::vector<std::pair<float*, float*>> gl;
-      for (int i = 0; i <= D; ++i) gl.push_back(gsq_for(pi.layers[i], 2 * i, 2 * i + 1));
-      std::vector<View> hsub(D), hzsub(D);
-      for (int i = 0; i < D; ++i) hsub[i] = h[i].sub(0, B);
-      if (pz)
-        for (int i = 0; i < D; ++i) hzsub[i] = hz[i].sub(0, B);
-      // TD3: the aliased target policy's Polyak (td3.py:200-204) in the Adam epilogues: one level
-      // fewer between the actor update and the next step's target action
-      adam_ptau = !sac && pi_polyak_fused() ? cfg.tau : 0.f;
-      adam_gscale = offline3() ? bc_s + 1 : nullptr;
-      // SAC: d1 (the gradient through the raw head, K = 2A <= 48) recomputed in-tile by d0's DX
-      const bool pld = sac && sac_bwd_fused() && prelayer_ok_dx(Lout, pi.layers[D - 1]);
-      View d = dx(pg, {{dout, &Lout, 0}}, HS[D - 1], B, actP, dsrc_of(actP, hsub[D - 1], hzsub[D - 1]),
-                  DxOpt().pre_gemm(prea ? &pdout : nullptr).pl_source(pld));
-      // (d0 reads the raw head's pre-update weights when it recomputes d1: emitted before that Adam)
-      const PreUse pd1 = pld ? pre_layer_dx(Lout, dout, hsub[D - 1]) : PreUse{};
-      View dp;
-      if (pld) dp = dx(pg, {{d, &pi.layers[D - 1], 0}}, HS[D - 2], B, actP, &hsub[D - 2], DxOpt().pre_gemm(&pd1));
-      dw(pg, Lout, dout, {hsub[D - 1]}, B, CNT_ADAM_PI, cfg.policy_lr, DwOpt().gsq_parts(gl[D]));
-      if (!pld) dp = dx(pg, {{d, &pi.layers[D - 1], 0}}, HS[D - 2], B, actP, dsrc_of(actP, hsub[D - 2], hzsub[D - 2]));
-      dw(pg, pi.layers[D - 1], d, {hsub[D - 2]}, B, CNT_ADAM_PI, cfg.policy_lr, DwOpt().gsq_parts(gl[D - 1]));
+        dzp0[n] = dx(pg, {{dzp0[n], &q[n]->layers[i], 0}}, HS[i - 1], B, actC,
+                     dsrc_of(actC, pc[n][i - 1], pcz[n][i - 1]), po);
+    const std::vector<DxTerm> ta0{{dzp0[0], &q[0]->layers[0], Sp}, {dzp0[1], &q[1]->layers[0], Sp}};
+    View dout;
+    PreUse pdout{};  // TD3: d1 recomputes dout in-tile
+    if (!sac) {
+      std::vector<DxTerm> ta = ta0;
+      // (offline: the cloning gradient, in the in-tile recomputation as well, so RLE_FUSE_PRE stays)
+      if (offline3()) ta.push_back({sb.bc_e, nullptr, 0, &sb.bc_eye});
+      dout = dx(pg, ta, A, B, ACT_TANH, &a_pi);
+      if (ac.prea) pdout = pre_actor_dx(ta, A, a_pi, 0);
+    } else if (sac_bwd_fused()) {  // the backward in the epilogue of the DX that forms da (one level fewer)
+      dout = buf(B, 2 * A);
+      SacBwdUse sbu{};
+      SacBwdArgs& a = sbu.a;
+      a.raw = raw.m;
+      a.eps2 = eps2.m;
+      a.dout = dout.m;
+      a.log_alpha = alpha_src();
+      a.alpha_lin = cfg.tmp >= 0.f;
+      a.inv_b = 1.f / (float)Bv;
+      a.nvalid = Bv;
+      a.min_log_std = cfg.min_log_std;
+      a.max_log_std = cfg.max_log_std;
+      a.mean_off = 0;
+      a.ls_off = A;
+      sbu.rd = {raw.id, eps2.id, R_LA};
+      sbu.wr = {dout.id};
+      dx(pg, ta0, A, B, DxOpt().sac_bwd(&sbu));
+    } else {
+      dout = buf(B, 2 * A);
+      View da = dx(pg, ta0, A, B);
+      Op op = sac_actor_op(OP_SAC_ACTOR_BWD, raw.m, Bv);  // (rows of the padded batch past Bv keep a zero gradient)
+      SacActorArgs& a = op.sac;
+      a.eps2 = eps2.m;
+      a.da = da.m;
+      a.dout = dout.m;
+      a.log_alpha = alpha_src();
+      a.alpha_lin = cfg.tmp >= 0.f;
+      a.inv_b = 1.f / (float)Bv;
+      pg.add(op, {raw.id, eps2.id, da.id, R_LA}, {dout.id});
+    }
+    int ngsq = 0;
+    if (!sac) {
+      // per-tile grad-square partials for norm/policy (rl/nn/utils.py:13-19)
+      for (auto& L : pi.layers) ngsq += dw_gsq_w(L) + dw_gsq_b(L);
+      sb.gsq = mem.make<float>(ngsq);
+    }
+    std::vector<int> tens;
+    float* gp = sb.gsq;
+    auto gsq_for = [&](const Layer& L, int t_w, int t_b) -> std::pair<float*, float*> {
+      if (!sb.gsq) return {nullptr, nullptr};
+      int nw = dw_gsq_w(L), nb = dw_gsq_b(L);
+      float* w = gp;
+      float* b = gp + nw;
+      gp += nw + nb;
+      for (int i = 0; i < nw; ++i) tens.push_back(t_w);
+      for (int i = 0; i < nb; ++i) tens.push_back(t_b);
+      return {w, b};
+    };
+    // actor backward: tensors in parameters() order mlp.0.w, mlp.0.b, mlp.2.w, ...
+    std::vector<std::pair<float*, float*>> gl;
+    for (int i = 0; i <= D; ++i) gl.push_back(gsq_for(pi.layers[i], 2 * i, 2 * i + 1));
+    std::vector<View> hsub(D), hzsub(D);
+    for (int i = 0; i < D; ++i) hsub[i] = ac.h[i].sub(0, B);
+    if (pz)
+      for (int i = 0; i < D; ++i) hzsub[i] = ac.hz[i].sub(0, B);
+    // What every weight gradient of the actor shares.  TD3: the aliased target policy's Polyak (td3.py:200-204)
+    // in the Adam epilogues: one level fewer between the actor update and the next step's target action.
+    // Offline TD3: the gradient scaled by lmbda (sb.bc_s[1])
+    const DwOpt ao = DwOpt().polyak(!sac && pi_polyak_fused() ? cfg.tau : 0.f)
+                         .grad_scale(offline3() ? sb.bc_s + 1 : nullptr, sb.bc_s_id);
+    // SAC: d1 (the gradient through the raw head, K = 2A <= 48) recomputed in-tile by d0's DX
+    const bool pld = sac && sac_bwd_fused() && prelayer_ok_dx(Lout, pi.layers[D - 1]);
+    View d = dx(pg, {{dout, &Lout, 0}}, HS[D - 1], B, actP, dsrc_of(actP, hsub[D - 1], hzsub[D - 1]),
+                DxOpt().pre_gemm(ac.prea ? &pdout : nullptr).pl_source(pld));
+    // (d0 reads the raw head's pre-update weights when it recomputes d1: emitted before that Adam)
+    const PreUse pd1 = pld ? pre_layer_dx(Lout, dout, hsub[D - 1]) : PreUse{};
+    View dp;
+    if (pld) dp = dx(pg, {{d, &pi.layers[D - 1], 0}}, HS[D - 2], B, actP, &hsub[D - 2], DxOpt().pre_gemm(&pd1));
+    dw(pg, Lout, dout, {hsub[D - 1]}, B, CNT_ADAM_PI, cfg.policy_lr, DwOpt(ao).gsq_parts(gl[D]));
+    if (!pld) dp = dx(pg, {{d, &pi.layers[D - 1], 0}}, HS[D - 2], B, actP, dsrc_of(actP, hsub[D - 2], hzsub[D - 2]));
+    dw(pg, pi.layers[D - 1], d, {hsub[D - 2]}, B, CNT_ADAM_PI, cfg.policy_lr, DwOpt(ao).gsq_parts(gl[D - 1]));
+    d = dp;
+    for (int i = D - 2; i >= 1; --i) {  // (deeper actors)
+      dp = dx(pg, {{d, &pi.layers[i], 0}}, HS[i - 1], B, actP, dsrc_of(actP, hsub[i - 1], hzsub[i - 1]));
+      dw(pg, pi.layers[i], d, {hsub[i - 1]}, B, CNT_ADAM_PI, cfg.policy_lr, DwOpt(ao).gsq_parts(gl[i]));
       d = dp;
-      for (int i = D - 2; i >= 1; --i) {  // (deeper actors)
-        dp = dx(pg, {{d, &pi.layers[i], 0}}, HS[i - 1], B, actP, dsrc_of(actP, hsub[i - 1], hzsub[i - 1]));
-        dw(pg, pi.layers[i], d, {hsub[i - 1]}, B, CNT_ADAM_PI, cfg.policy_lr, DwOpt().gsq_parts(gl[i]));
-        d = dp;
-      }
-      dw(pg, pi.layers[0], d, {s}, B, CNT_ADAM_PI, cfg.policy_lr, DwOpt().gsq_parts(gl[0]));
-      adam_ptau = 0.f;
-      adam_gscale = nullptr;
-      if (gsq) {
-        // tensor t owns tiles [gsq_offs[t], gsq_offs[t+1]) (params() order: w0, b0, w1, b1, ...)
-        gsq_offs.assign(1, 0);
-        for (size_t i = 0; i < tens.size(); ++i)
-          if (i + 1 == tens.size() || tens[i + 1] != tens[i]) gsq_offs.push_back((int)i + 1);
-      }
     }
-    // Polyak (td3.py:194-204 on policy steps incl. aliased policy Q2; sac.py:243-249 every step)
-    if (!sac && policy) {
-      flat(pg, OP_POLYAK, *tq[0], q[0], cfg.tau, false);
-      flat(pg, OP_POLYAK, *tq[1], q[1], cfg.tau, false);
-      if (!pi_polyak_fused()) flat(pg, OP_POLYAK, pi, nullptr, cfg.tau, true);
+    dw(pg, pi.layers[0], d, {s}, B, CNT_ADAM_PI, cfg.policy_lr, DwOpt(ao).gsq_parts(gl[0]));
+    if (sb.gsq) {
+      // tensor t owns tiles [gsq_offs[t], gsq_offs[t+1]) (params() order: w0, b0, w1, b1, ...)
+      sb.gsq_offs.assign(1, 0);
+      for (size_t i = 0; i < tens.size(); ++i)
+        if (i + 1 == tens.size() || tens[i + 1] != tens[i]) sb.gsq_offs.push_back((int)i + 1);
     }
-    if (sac) {
-      flat(pg, OP_POLYAK, *tq[0], q[0], cfg.tau, false);
-      flat(pg, OP_POLYAK, *tq[1], q[1], cfg.tau, false);
-    }
-    // step end
+  }
+  // Polyak (td3.py:194-204 on policy steps incl. the aliased policy, Q2; sac.py:243-249 every step)
+  void mlp_polyak(Prog& pg, const StepBuild& sb) {
+    const bool sac = algo == RLE_SAC;
+    if (!sac && !sb.policy) return;
+    flat(pg, OP_POLYAK, net("target_q1"), &net("q1"), cfg.tau, false);
+    flat(pg, OP_POLYAK, net("target_q2"), &net("q2"), cfg.tau, false);
+    if (!sac && !pi_polyak_fused()) flat(pg, OP_POLYAK, net("policy"), nullptr, cfg.tau, true);
+  }
+  // Step end: the info row of the algorithm (and the SAC temperature update)
+  void mlp_step_end(Prog& pg, const StepBuild& sb) {
+    const bool sac = algo == RLE_SAC, policy = sb.policy;
+    float* const ploss_part = sb.ploss.p;
+    const int hw = cdiv(B, 4);
     Op op = step_end_op();
     StepEndArgs& a = op.end;
-    std::vector<int> rd{qloss_id};
-    if (policy) rd.push_back(ploss_id);
+    std::vector<int> rd{sb.qloss.id};
+    if (policy) rd.push_back(sb.ploss.id);
     if (!sac) {  // [train/q_fn, train/policy, norm/policy]
-      info_sum(a, 0, qloss_part, hw * 4, 1, (lap ? 1.f : 0.5f) / (float)Bv);
+      info_sum(a, 0, sb.qloss.p, sb.qloss.n, 1, (cfg.use_lap ? 1.f : 0.5f) / (float)Bv);
       if (policy) {
         info_sum(a, 1, ploss_part, hw, 4, -1.f / (float)Bv);
         a.kind[2] = INFO_GNORM;
-        a.gsq = gsq;
-        a.ngsq_t = (int)gsq_offs.size() - 1;
-        for (size_t q = 0; q < gsq_offs.size(); ++q) a.gsq_off[q] = gsq_offs[q];
-        for (auto& L : pi.layers) rd.push_back(L.res);
+        a.gsq = sb.gsq;
+        a.ngsq_t = (int)sb.gsq_offs.size() - 1;
+        for (size_t q = 0; q < sb.gsq_offs.size(); ++q) a.gsq_off[q] = sb.gsq_offs[q];
+        for (auto& L : net("policy").layers) rd.push_back(L.res);
       } else {
         a.kind[1] = INFO_NAN;
         a.kind[2] = INFO_NAN;
       }
       a.ninfo = 3;
-      if (offline3()) {  // [train/q_fn, train/policy, norm/policy, train/bc, train/lmbda]
-        a.ninfo = 5;
-        if (policy) {
-          a.kind[1] = INFO_SUM_BC3;  // lmbda * -mean(min Q) + bc
-          a.bcs = bc_s;
-          info_sum(a, 3, bc_part, bc_part_n, 1, 1.f / ((float)Bv * (float)A));
-          a.kind[4] = INFO_BCS1;
-          rd.push_back(bc_s_id);
-          rd.push_back(bc_part_id);
-        } else {
-          a.kind[3] = a.kind[4] = INFO_NAN;
-        }
-      }
+      if (offline3()) info_offline(a, rd, sb);
     } else if (cfg.tmp < 0.f) {  // [train/q_fn, tmp, norm/tmp, train/policy, train/tmp, entropy]
-      info_sum(a, 0, qloss_part, hw * 4, 1, 0.5f / (float)Bv);
+      info_sum(a, 0, sb.qloss.p, sb.qloss.n, 1, 0.5f / (float)Bv);
       a.kind[1] = INFO_SAC_TMP;
       a.kind[2] = INFO_SAC_NTMP;
       info_sum(a, 3, ploss_part, hw, 4, 1.f / (float)Bv);
@@ -4461,7 +4422,7 @@ struct Engine {
       a.logpi_part = ploss_part;
       a.nlogpi = hw;
     } else {  // fixed temperature: [train/q_fn, train/policy, entropy]
-      info_sum(a, 0, qloss_part, hw * 4, 1, 0.5f / (float)Bv);
+      info_sum(a, 0, sb.qloss.p, sb.qloss.n, 1, 0.5f / (float)Bv);
       info_sum(a, 1, ploss_part, hw, 4, 1.f / (float)Bv);
       a.kind[2] = INFO_SAC_ENT;
       a.ninfo = 3;
@@ -4472,7 +4433,16 @@ struct Engine {
     if (policy) cn.push_back(CNT_ADAM_PI);
     add_step_end(pg, op, rd, cn);
   }
-  std::vector<int> gsq_offs;
+  void build_mlp(Prog& pg, bool policy, int set) {
+    StepBuild sb = begin_step(pg, policy, set);
+    const MlpActor ac = mlp_actor(pg);
+    const MlpCritics cr = mlp_critics(pg, sb, ac);
+    mlp_critic_backward(pg, sb, cr);
+    if (policy) mlp_policy(pg, sb, ac);
+    mlp_polyak(pg, sb);
+    mlp_step_end(pg, sb);
+  }
+
 
   // ---------------------------------------------------------------- graphs
   // Workgroup cap of the scheduler's levels: off by default.  Measured on MI355X: neutral at

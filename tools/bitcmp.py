@@ -4,9 +4,11 @@
     RLE_LIB=lib_b.so python tools/bitcmp.py dump NAME STEPS out_b.npz
     python tools/bitcmp.py cmp out_a.npz out_b.npz [out_a_again.npz]
 
-NAME: a golden of tests/golden, or edge:<case> for a case of tests/edge_cases.py (built under edge_env,
-as tests/test_shape_edges_gpu.py builds it).  Per step: every parameter, the priorities and the info row
-after a single-step replay.  The dump also holds the programs' descriptions (rle_graph_describe 0, 1, 3
+NAME: a golden of tests/golden, edge:<case> for a case of tests/edge_cases.py (built under edge_env,
+as tests/test_shape_edges_gpu.py builds it), or offline3:<shape> for an offline TD3 (TD3+BC) engine over a shape
+of tests/test_offline_td3_gpu.py's SHAPES (its _env, offline_engine, ALPHA and tapes: OP_BC modes 2 and 3 and the
+kDwGs weight gradients, which no golden or edge case builds).  Per step: every parameter, the priorities and the
+info row after a single-step replay.  The dump also holds the programs' descriptions (rle_graph_describe 0, 1, 3
 and the hard-update program; empty where the engine has none) -- with RLE_DESC_WG=1 in the environment
 they carry every op's workgroup count, so a changed tile plan shows even where the floats agree.
 
@@ -27,6 +29,7 @@ sys.path[:0] = [REPO, os.path.join(REPO, "sac-td3-td7_amd"), os.path.join(REPO, 
 
 OPT_IN = ("priosample",)  # include/rle.h RLE_FUSE_OPT_IN: off unless asked for, so not part of "all"
 DESCRIBE = {"desc_policy": 0, "desc_plain": 1, "desc_multi": 3, "desc_hard": 2}
+OFFLINE3_STEPS = 6  # steps of an offline3: trajectory (policy steps 1, 3, 5, as the offline TD3 tests run)
 
 
 def plan_from_env():
@@ -44,6 +47,20 @@ def build(name, plan):
     from harness import engine_from_golden
     from oracle import spec
 
+    if name.startswith("offline3:"):
+        import test_offline_td3_gpu as T
+
+        shape = name[9:]
+        g = {k: v for k, v in T.SHAPES[shape]().items() if not k.startswith("tape_")}
+        with T._env(shape):
+            S, A = spec.TASKS[str(g["meta_env"])][:2]
+            eng, rep = T.offline_engine(g, T.ALPHA, plan)
+        # (the tests' own tapes, for every shape as they run it: the synthetic shapes have none)
+        g["meta"] = np.array(g["meta"])
+        g["meta"][4] = OFFLINE3_STEPS
+        tapes = T._tapes(OFFLINE3_STEPS, int(g["meta"][1]), A, int(g["meta"][6]))
+        g.update({"tape_" + k: v for k, v in tapes.items()})
+        return g, eng, rep, S, A
     if not name.startswith("edge:"):
         from conftest import load_golden
 
