@@ -56,11 +56,12 @@ typedef struct rle_config {
   int n_hidden;             /* TD3/SAC: hidden layers of make_mlp (mlp.py:10-35), 2..RLE_MAX_HIDDEN; 0 = two
                                layers of `hidden` (mlp.py:45-47) */
   int hidden_sizes[8];      /* TD3/SAC: their widths, input side first (each a multiple of 4, <= 512) */
-  /* Hidden-layer activations (RLE_ACT_*; 0 = the reference default of that net).  TD7: SALEActor / SALECritic /
+  /* Hidden-layer activations (RLE_ACT_*: ReLU, ELU, Identity, LeakyReLU, SiLU, GELU; 0 = the reference default of
+     that net), forward and backward as torch computes them in fp32.  TD7: SALEActor / SALECritic /
      SALEEncoder `activ` (sale.py:25,67,97: ReLU / ELU / ELU); TD3/SAC: make_mlp's action_fn of the policy and of the
      critics (mlp.py:13, default ReLU; act_encoder must be 0).  A non-default activation runs its programs on the
-     extended kernel instance without RLE_FUSE_PRELAYER, PRE, TWOSTAGE and SACPRE (and, for identity critics, without
-     QDOT and HEADDX). */
+     extended kernel instance (LeakyReLU / SiLU / GELU: on a copy of it that also holds their variants) without
+     RLE_FUSE_PRELAYER, PRE, TWOSTAGE and SACPRE (and, for identity critics, without QDOT and HEADDX). */
   int act_actor, act_critic, act_encoder;
   /* TD7 offline mode (the paper's behaviour-cloning term; the reference names it, rl/cli.py:110-123, and does
      not implement it): on policy steps the actor objective is
@@ -106,6 +107,11 @@ typedef struct rle_config_ext {
 #define RLE_ACT_RELU 1
 #define RLE_ACT_ELU 2       /* alpha = 1 (F.elu / nn.ELU defaults) */
 #define RLE_ACT_IDENTITY 3  /* action_fn "Identity" / nn.Identity(): no activation between the Linear layers */
+#define RLE_ACT_LEAKY_RELU 4 /* negative_slope = 0.01 (F.leaky_relu / nn.LeakyReLU defaults) */
+#define RLE_ACT_SILU 5
+#define RLE_ACT_GELU 6      /* the exact erf form (F.gelu / nn.GELU defaults, approximate "none") */
+/* Any other code is RLE_EINVAL.  Not run: Tanh as a hidden activation, other slopes / alphas, GELU's tanh
+   approximation, and every other activation. */
 
 /* Step-program plan: the schedule and tile-plan choices that decide how the step's reductions are
  * split (so its fp32 summation order) and how its ops are fused.  Every engine starts from the

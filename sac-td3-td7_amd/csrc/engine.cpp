@@ -336,7 +336,7 @@ static void xcd_plan(GemmArgs& g, bool xcd);
 // (ks < 0: in any kernel set)
 static bool gemm_variant_compiled(int vid, int ks = -1) {
 #define RLE_VID(mode, epi, act, norm, pre, pk, sets) \
-  (vid == gemm_vid(mode, epi, act, norm, pre) && (ks < 0 || ks == KS_EXT || (((sets) >> ks_family(ks)) & 1))) ||
+  (vid == gemm_vid(mode, epi, act, norm, pre) && (ks < 0 || ks_family(ks) == KS_EXT || (((sets) >> ks_family(ks)) & 1))) ||
   return RLE_GEMM_VARIANTS(RLE_VID) false;
 #undef RLE_VID
 }
@@ -347,7 +347,13 @@ static void gemm_finalize(GemmArgs& g, bool xcd = true) {
   int norm = 0;
   for (int q = 0; q < g.A.nseg; ++q) norm |= g.A.seg[q].norm.part != nullptr;
   for (int q = 0; q < g.B.nseg; ++q) norm |= g.B.seg[q].norm.part != nullptr;
-  const int act = g.mode == GEMM_FWD ? g.act : (g.mode == GEMM_DX ? g.dact : g.act);
+  // (act: the id's activation field; an activation past ACT_TANH, act_rt, takes ELU's -- ops.h act_vslot)
+  const int act_rt = g.mode == GEMM_FWD ? g.act : (g.mode == GEMM_DX ? g.dact : ACT_NONE);
+  const int act = g.mode == GEMM_DW ? g.act : act_vslot(act_rt);
+  REQUIRE(act_rt >= ACT_NONE && act_rt <= ACT_GELU, "gemm: activation");
+  REQUIRE(act_rt <= ACT_TANH || ((g.has_pre == 0 || g.has_pre == 2) &&
+                                 (g.epi == EPI_STORE || g.epi == EPI_QDOT || g.epi == EPI_QHEAD)),
+          "gemm: LeakyReLU / SiLU / GELU run the plain and fused-loss-head paths only (kernels.hip kActRt)");
   REQUIRE(g.mode != GEMM_DX || !norm, "gemm: no DX variant with normed operands");
   REQUIRE(g.mode != GEMM_DW || g.epi == EPI_ADAM, "gemm: DW is always fused with Adam");
   REQUIRE(g.mode != GEMM_DW || act == ACT_NONE || (act == kDwGs && !norm && g.gscale) ||
@@ -371,7 +377,7 @@ static void gemm_finalize(GemmArgs& g, bool xcd = true) {
     const bool parts = h.qp[0] && h.qp[1] && h.qp_n[0] <= 64 && h.qp_n[1] <= 64 &&
                        (pol || (h.tp[0] && h.tp[1] && h.tp_n[0] <= 64 && h.tp_n[1] <= 64));
     REQUIRE(g.has_pre != 2 || (g.mode == GEMM_DX && g.epi == EPI_STORE && (act == ACT_ELU || act == ACT_RELU) &&
-                               !norm && g.A.nseg == 1 && modes && parts && h.dact == act && (!h.sac || h.logpi) &&
+                               !norm && g.A.nseg == 1 && modes && parts && h.dact == act_rt && (!h.sac || h.logpi) &&
                                (!h.lap || h.prio) && h.H <= 256 && h.H % 4 == 0 && g.R == r16(h.H) &&
                                g.M % 16 == 0 && h.rows == h.nvalid && h.rows <= g.M && g.M - h.rows < 16 &&
                                (g.head_n == 0 || g.head_n == 1)),
@@ -1741,6 +1747,8 @@ struct Engine {
   // the rle_level instance this engine's programs run on (ops.h KernelSet): the agent's own set, or the
   // extended instance when the plan asks for its opt-in paths
   int kernel_set() const {
+    // (LeakyReLU / SiLU / GELU: the ELU variants' second dispatch is KS_ACT's alone, ops.h act_vslot)
+    if (std::max({actP, actC, actE}) > ACT_TANH) return KS_ACT;
     if (!acts_default) return KS_EXT;  // (the activation variants outside the agent's own set)
     // (offline TD3: OP_BC modes 2 / 3, the kDwGs variant, the |min| slot and the info kinds are the extended
     // instance's alone, so the TD3 / SAC instance is byte for byte what the online programs ran on before)
@@ -1804,10 +1812,11 @@ struct Engine {
   // hidden activations (ops.h Act) of the actor, the critics and TD7's encoders (rle_config act_*)
   int actP = ACT_RELU, actC = ACT_ELU, actE = ACT_ELU;
   bool acts_default = true;
-  // The derivative source of a hidden activation for an input-gradient GEMM: ELU' = exp(z) reads the pre-activation
-  // z (as autograd's elu_backward does), ReLU' the output, identity none.
+  // The derivative source of a hidden activation for an input-gradient GEMM: ELU' = exp(z), and LeakyReLU', SiLU',
+  // GELU' likewise (ops.h act_zsaved), read the pre-activation z (as autograd's backward does), ReLU' the output,
+  // identity none.
   static const View* dsrc_of(int act, const View& y, const View& z) {
-    return act == ACT_ELU ? &z : act == ACT_RELU ? &y : nullptr;
+    return act_zsaved(act) ? &z : act == ACT_RELU ? &y : nullptr;
   }
   int algo;
   hipStream_t stream = nullptr;
@@ -2723,7 +2732,7 @@ struct Engine {
     if (o.qdot) {  // EPI_QDOT: row partials of the H -> 1 layer qdot applied to this output
       // (qdot->K is the padded width: the kernel zeroes the weights of the columns past L.out, j < N)
       REQUIRE(!o.normed && o.qdot->out == 1 && o.qdot->K == r16(L.out) &&
-                  (act == ACT_ELU || act == ACT_RELU || act == ACT_NONE),
+                  (act_zsaved(act) || act == ACT_RELU || act == ACT_NONE),
               "fwd: q-dot partial layout");
       qpart = mem.make<float>((size_t)tiles_n * M);
       out.qd = qpart;
@@ -3672,7 +3681,7 @@ struct Engine {
     View fa2 = fwd(pg, fe.layers[4], {{fa1}}, B, actE, fo);
     o.fzsa = fwd(pg, fe.layers[5], {{fa2}}, B, ACT_NONE);
     o.ap0 = fwd(pg, pi.layers[0], {{ss}}, B2, ACT_NONE, FwdOpt().norm());
-    const bool pz = actP == ACT_ELU;
+    const bool pz = act_zsaved(actP);
     o.ap1 = fwd(pg, pi.layers[1], {{o.ap0}, {o.fzs, o.tzs}}, B2, actP, FwdOpt().keep_pre(pz ? &o.ap1z : nullptr));
     o.ap2 = fwd(pg, pi.layers[2], {{o.ap1}}, B2, actP, FwdOpt().keep_pre(pz ? &o.ap2z : nullptr));
     // a' = clamp(pi(s', zs') + noise) only feeds the target branch's first layers, which
@@ -3858,7 +3867,7 @@ struct Engine {
     // input-grads through a layer are emitted BEFORE its Adam update so the
     // scheduler orders them against the pre-update weights (as autograd does)
     View ap2s = ac.ap2.sub(0, B), ap1s = ac.ap1.sub(0, B);
-    const View ap2zs = actP == ACT_ELU ? ac.ap2z.sub(0, B) : View{}, ap1zs = actP == ACT_ELU ? ac.ap1z.sub(0, B) : View{};
+    const View ap2zs = act_zsaved(actP) ? ac.ap2z.sub(0, B) : View{}, ap1zs = act_zsaved(actP) ? ac.ap1z.sub(0, B) : View{};
     View dl2 = dx(pg, {{dl3, &pi.layers[3], 0}}, H, B, actP, dsrc_of(actP, ap2s, ap2zs),
                   DxOpt().pre_gemm(ac.prea ? &p3 : nullptr));
     dw(pg, pi.layers[3], dl3, {ap2s}, B, CNT_ADAM_PI, cfg.policy_lr);
@@ -4007,7 +4016,7 @@ struct Engine {
     const int D = (int)Q.layers.size() - 1;
     hs.assign(D, View{});
     if (hz) hz->assign(D, View{});
-    auto zp = [&](int i) { return hz && actC == ACT_ELU ? &(*hz)[i] : nullptr; };
+    auto zp = [&](int i) { return hz && act_zsaved(actC) ? &(*hz)[i] : nullptr; };
     const bool shape = prelayer_shape(Q.layers[0], Q.layers[1]);
     // (the pre-GEMM's a' segment is one column block, kernels.hip PK 4 / gemm_finalize's two-stage REQUIRE)
     const bool two = pre && pre->kind == 1 && pre->a.mode == GEMM_FWD && pre->a.N <= 32 && r16(A) <= 16 && qd &&
@@ -4093,7 +4102,7 @@ struct Engine {
     MlpActor o;
     std::vector<View>&h = o.h, &hz = o.hz;
     h.resize(D), hz.resize(D);
-    const bool pz = actP == ACT_ELU;
+    const bool pz = act_zsaved(actP);
     const bool pl01 = prelayer_ok(pi.layers[0], pi.layers[1]);  // (the second layer recomputes the first in-tile)
     h[0] = fwd(pg, pi.layers[0], {{ss}}, B2, actP, FwdOpt().keep_pre(pz ? &hz[0] : nullptr).pl_source(pl01));
     const PreUse pl0 = pl01 ? pre_layer(pi.layers[0], {ss}) : PreUse{};
@@ -4166,7 +4175,7 @@ struct Engine {
     for (int n = 0; n < 2; ++n)
       mlp_critic_fwd(pg, *q[n], sb.s, act_in, o.c[n], /*out_t*/ true, nullptr, true, o.hdx, &o.cz[n]);
     // (the loss head's derivative rows: ELU' reads the pre-activation; ReLU' / identity the output)
-    const bool cze = actC == ACT_ELU;
+    const bool cze = act_zsaved(actC);
     // (the last hidden layers and the heads' layers)
     const View c1[2] = {o.c[0][D - 1], o.c[1][D - 1]}, th1[2] = {th[0][D - 1], th[1][D - 1]};
     const View cz1[2] = {o.cz[0][D - 1], o.cz[1][D - 1]};
@@ -4219,7 +4228,7 @@ struct Engine {
     const Layer& Lout = pi.layers[D];
     const Layer* qo[2] = {&q[0]->layers[D], &q[1]->layers[D]};
     const View &s = sb.s, &a_pi = ac.a_pi, &raw = ac.raw;
-    const bool hdx = mlp_headdx(), cze = actC == ACT_ELU, pz = actP == ACT_ELU;
+    const bool hdx = mlp_headdx(), cze = act_zsaved(actC), pz = act_zsaved(actP);
     std::vector<View> pc[2], pcz[2];
     for (int n = 0; n < 2; ++n)
       mlp_critic_fwd(pg, *q[n], s, a_pi, pc[n], /*out_t*/ true, nullptr, /*last_t*/ false, hdx, &pcz[n]);
@@ -4511,7 +4520,11 @@ struct Engine {
                            : op.gemm.has_pre == 5                         ? "st+sacpre"
                                                                            : kepi[op.gemm.epi];
           G.desc += "[" + std::to_string(op.gemm.M) + "x" + std::to_string(op.gemm.N) + "x" +
-                    std::to_string(op.gemm.R) + " " + ep + (op.gemm.hot.wide ? ".w" : "") + "]";
+                    std::to_string(op.gemm.R) + " " + ep + (op.gemm.hot.wide ? ".w" : "");
+          // (an activation past ACT_TANH runs the kActRt instantiation under its ELU id: named, the others are not)
+          const int art = op.gemm.mode == GEMM_FWD ? op.gemm.act : op.gemm.mode == GEMM_DX ? op.gemm.dact : ACT_NONE;
+          if (art > ACT_TANH) G.desc += art == ACT_LEAKY ? " leaky" : art == ACT_SILU ? " silu" : " gelu";
+          G.desc += "]";
         }
         if (std::getenv("RLE_DESC_WG")) G.desc += "/" + std::to_string(op.wg_count);  // trace tools
       }
@@ -4523,6 +4536,12 @@ struct Engine {
       for (auto& op : lv) {
         REQUIRE(op.kind != OP_GEMM || gemm_variant_compiled(op.gemm.vid, kernel_set()),
                 "capture: a GEMM variant outside the engine's rle_level instance (ops.h RLE_GEMM_VARIANTS sets)");
+        // (LeakyReLU / SiLU / GELU: the second dispatch under the ELU ids is the KS_ACT instance's alone)
+        REQUIRE(kernel_set() == KS_ACT ||
+                    ((op.kind != OP_GEMM || op.gemm.mode == GEMM_DW ||
+                      (op.gemm.mode == GEMM_FWD ? op.gemm.act : op.gemm.dact) <= ACT_TANH) &&
+                     (op.kind != OP_HEAD || op.head.dact <= ACT_TANH)),
+                "capture: an activation of the KS_ACT rle_level instance in another instance's program");
         flat_ops.push_back(op);
       }
     G.d_ops = mem.make<Op>(total);
@@ -5592,7 +5611,7 @@ int rle_create_ext(const rle_config* cfg, const rle_config_ext* ext, rle_engine*
       REQUIRE(cfg->hidden_sizes[i] > 0 && cfg->hidden_sizes[i] <= 512 && cfg->hidden_sizes[i] % 4 == 0,
               "create: hidden_sizes must be multiples of 4, <= 512");
     for (int a : {cfg->act_actor, cfg->act_critic, cfg->act_encoder})
-      REQUIRE(a >= RLE_ACT_DEFAULT && a <= RLE_ACT_IDENTITY, "create: activation must be an RLE_ACT_* code");
+      REQUIRE(a >= RLE_ACT_DEFAULT && a <= RLE_ACT_GELU, "create: activation must be an RLE_ACT_* code");
     REQUIRE(cfg->algo == RLE_TD7 || cfg->act_encoder == RLE_ACT_DEFAULT, "create: act_encoder is TD7's (SALEEncoder)");
     REQUIRE(cfg->bc_lambda >= 0.f && std::isfinite(cfg->bc_lambda), "create: bc_lambda must be a finite value >= 0");
     REQUIRE(cfg->bc_lambda == 0.f || cfg->algo == RLE_TD7, "create: bc_lambda (offline mode) is TD7's");
@@ -5624,7 +5643,10 @@ int rle_create_ext(const rle_config* cfg, const rle_config_ext* ext, rle_engine*
       return code == RLE_ACT_RELU ? rle::ACT_RELU
              : code == RLE_ACT_ELU ? rle::ACT_ELU
              : code == RLE_ACT_IDENTITY ? rle::ACT_NONE
-                                        : dflt;
+             : code == RLE_ACT_LEAKY_RELU ? rle::ACT_LEAKY
+             : code == RLE_ACT_SILU ? rle::ACT_SILU
+             : code == RLE_ACT_GELU ? rle::ACT_GELU
+                                    : dflt;
     };
     const bool td7 = e.algo == RLE_TD7;
     e.actP = act_of(cfg->act_actor, rle::ACT_RELU);

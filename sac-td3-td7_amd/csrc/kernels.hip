@@ -192,22 +192,45 @@ __device__ __forceinline__ float norm_m(const float* part, int ld, int row, int 
   return m < 1e-8f ? 1e-8f : m;
 }
 
+// The hidden activations past ACT_TANH (ops.h act_zsaved: LeakyReLU slope 0.01, SiLU, exact GELU), forward and
+// derivative, both from the pre-activation z as torch's kernels compute them in fp32.
+__device__ __forceinline__ float act_fwd_z(int act, float z) {
+  if (act == ACT_LEAKY) return z > 0.f ? z : z * 0.01f;
+  if (act == ACT_SILU) return z / (1.f + expf(-z));
+  return (z * 0.5f) * (1.f + erff(z * 0.70710678118654752440f));  // ACT_GELU
+}
+__device__ __forceinline__ float act_bwd_z(int act, float z) {
+  if (act == ACT_LEAKY) return z > 0.f ? 1.f : 0.01f;
+  if (act == ACT_SILU) {
+    const float s = 1.f / (1.f + expf(-z));
+    return s * (1.f + z * (1.f - s));
+  }
+  const float cdf = 0.5f * (1.f + erff(z * 0.70710678118654752440f));  // ACT_GELU: Phi(z) + z phi(z)
+  return cdf + z * (expf(-0.5f * z * z) * 0.39894228040143267794f);
+}
+
 __device__ __forceinline__ float act_fwd(int act, float v) {
   switch (act) {
     case ACT_RELU: return v > 0.f ? v : 0.f;
     case ACT_ELU: return v > 0.f ? v : expm1f(v);
     case ACT_TANH: return tanhf(v);
+    case ACT_LEAKY:
+    case ACT_SILU:
+    case ACT_GELU: return act_fwd_z(act, v);
     default: return v;
   }
 }
 
-// Derivative mask given the saved tensor: ReLU/tanh from the output H,
-// ELU from the pre-activation Z (torch elu_backward uses the input).
+// Derivative mask given the saved tensor: ReLU/tanh from the output H, ELU and the activations
+// past ACT_TANH from the pre-activation Z (torch's backward kernels use the input).
 __device__ __forceinline__ float act_bwd(int act, float saved) {
   switch (act) {
     case ACT_RELU: return saved > 0.f ? 1.f : 0.f;
     case ACT_ELU: return saved > 0.f ? 1.f : expf(saved);
     case ACT_TANH: return 1.f - saved * saved;
+    case ACT_LEAKY:
+    case ACT_SILU:
+    case ACT_GELU: return act_bwd_z(act, saved);
     default: return 1.f;
   }
 }
@@ -393,18 +416,25 @@ __device__ __forceinline__ float4 mul4(float4 v, float4 s) {
   return make_float4(v.x * s.x, v.y * s.y, v.z * s.z, v.w * s.w);
 }
 
+// kActRt in the ACT slot of a template: one of the activations past ACT_TANH, named at run time by the op's own
+// field (rt: GemmArgs::act / dact, HeadArgs::dact; workgroup-uniform).  The variant id has no room for them, so an
+// op with one carries the ELU id -- ELU's paths keep the pre-activation and differentiate from it, which is what
+// these need -- and the KS_ACT instance picks the kActRt instantiation under that id (op_gemm, op_head).
+constexpr int kActRt = 7;
 template <int ACT>
-__device__ __forceinline__ float act_f(float v) {
+__device__ __forceinline__ float act_f(float v, int rt = ACT_NONE) {
   if constexpr (ACT == ACT_RELU) return v > 0.f ? v : 0.f;
   else if constexpr (ACT == ACT_ELU) return v > 0.f ? v : expm1f(v);
   else if constexpr (ACT == ACT_TANH) return tanhf(v);
+  else if constexpr (ACT == kActRt) return act_fwd_z(rt, v);
   else return v;
 }
 template <int ACT>
-__device__ __forceinline__ float act_b(float saved) {  // see act_bwd
+__device__ __forceinline__ float act_b(float saved, int rt = ACT_NONE) {  // see act_bwd
   if constexpr (ACT == ACT_RELU) return saved > 0.f ? 1.f : 0.f;
   else if constexpr (ACT == ACT_ELU) return saved > 0.f ? 1.f : expf(saved);
   else if constexpr (ACT == ACT_TANH) return 1.f - saved * saved;
+  else if constexpr (ACT == kActRt) return act_bwd_z(rt, saved);
   else return 1.f;
 }
 
@@ -1133,8 +1163,8 @@ __device__ __forceinline__ f32x4 headdx_reduce(const CAS GemmArgs& g, int i0, in
       if (c + r >= n) break;  // (uniform, as ring_run)
       const int k = c0 + c + r;  // absolute chunk
       const float4 z = xa[r], w = *(const float4*)(w3s + k * 16 + cq);
-      const float4 y = make_float4((dqr * w.x) * act_b<DACT>(z.x), (dqr * w.y) * act_b<DACT>(z.y),
-                                   (dqr * w.z) * act_b<DACT>(z.z), (dqr * w.w) * act_b<DACT>(z.w));
+      const float4 y = make_float4((dqr * w.x) * act_b<DACT>(z.x, h.dact), (dqr * w.y) * act_b<DACT>(z.y, h.dact),
+                                   (dqr * w.z) * act_b<DACT>(z.z, h.dact), (dqr * w.w) * act_b<DACT>(z.w, h.dact));
       if (own_dz) mat_str4(h.dz[hn], i0 + (lane & 15), k * 16 + cq, y);
       if (r & 1) acc1 = mfma4(y, xb[r], acc1);
       else acc = mfma4(y, xb[r], acc);
@@ -1357,10 +1387,10 @@ __device__ __forceinline__ void gemm_wide(const CAS GemmArgs& g, int t, float* s
         if constexpr (MODE == GEMM_FWD) {
           if (g.pre.t) mat_st4(g.pre, ib, j, make_float4(y[0], y[1], y[2], y[3]));
 #pragma unroll
-          for (int qq = 0; qq < 4; ++qq) y[qq] = act_f<ACT>(y[qq]);
+          for (int qq = 0; qq < 4; ++qq) y[qq] = act_f<ACT>(y[qq], g.act);
         } else {
 #pragma unroll
-          for (int qq = 0; qq < 4; ++qq) y[qq] *= act_b<ACT>(e4[qq]);
+          for (int qq = 0; qq < 4; ++qq) y[qq] *= act_b<ACT>(e4[qq], g.dact);
         }
 #pragma unroll
         for (int qq = 0; qq < 4; ++qq) rv[qq] = EPI == EPI_QDOT ? y[qq] * qwj[c] : fabsf(y[qq]);
@@ -1377,10 +1407,10 @@ __device__ __forceinline__ void gemm_wide(const CAS GemmArgs& g, int t, float* s
         float dz[4];
 #pragma unroll
         for (int qq = 0; qq < 4; ++qq) {
-          const float z = acc[qq] + pb[c], y = act_f<ACT>(z);
+          const float z = acc[qq] + pb[c], y = act_f<ACT>(z, g.act);
           const bool rv = ib + qq < g.mvalid;  // (rows of the padded batch past it add nothing)
           lv += rv ? y * qwj[c] : 0.f;
-          dz[qq] = rv ? (g.qscale * qwj[c]) * act_b<ACT>(ACT == ACT_RELU ? y : z) : 0.f;
+          dz[qq] = rv ? (g.qscale * qwj[c]) * act_b<ACT>(ACT == ACT_RELU ? y : z, g.act) : 0.f;
         }
         mat_st4(g.out, ib, j, make_float4(dz[0], dz[1], dz[2], dz[3]));
       }
@@ -1920,7 +1950,7 @@ __device__ __forceinline__ void gemm_v(const CAS GemmArgs& g, int t, float* smem
         if constexpr (MODE == GEMM_FWD) {
           if (g.pre.t) mat_st4(g.pre, ib, j, make_float4(y[0], y[1], y[2], y[3]));
 #pragma unroll
-          for (int q = 0; q < 4; ++q) y[q] = act_f<ACT>(y[q]);
+          for (int q = 0; q < 4; ++q) y[q] = act_f<ACT>(y[q], g.act);
           if constexpr (ACT == ACT_TANH) {
             if (g.noise.t && ib >= g.noise_row0) {  // target policy smoothing (td7.py:188-194)
               const float4 e = mat_ld4(g.noise, ib - g.noise_row0, j);
@@ -1935,7 +1965,7 @@ __device__ __forceinline__ void gemm_v(const CAS GemmArgs& g, int t, float* smem
         } else {  // DX: derivative mask
           const float dv[4] = {ds.x, ds.y, ds.z, ds.w};
 #pragma unroll
-          for (int q = 0; q < 4; ++q) y[q] *= act_b<ACT>(dv[q]);
+          for (int q = 0; q < 4; ++q) y[q] *= act_b<ACT>(dv[q], g.dact);
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) rowabs[q] = EPI == EPI_QDOT ? y[q] * qwj : fabsf(y[q]);
@@ -2043,10 +2073,10 @@ __device__ __forceinline__ void gemm_v(const CAS GemmArgs& g, int t, float* smem
       float dz[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const float z = acc[q] + pre_b, y = act_f<ACT>(z);
+        const float z = acc[q] + pre_b, y = act_f<ACT>(z, g.act);
         const bool rv = ib + q < g.mvalid;  // (rows of the padded batch past it add nothing)
         ls += rv ? y * qwj : 0.f;
-        dz[q] = rv ? (g.qscale * qwj) * act_b<ACT>(ACT == ACT_RELU ? y : z) : 0.f;
+        dz[q] = rv ? (g.qscale * qwj) * act_b<ACT>(ACT == ACT_RELU ? y : z, g.act) : 0.f;
       }
       mat_st4(g.out, ib, j, make_float4(dz[0], dz[1], dz[2], dz[3]));
     }
@@ -2184,15 +2214,27 @@ __device__ __forceinline__ void gemm_v(const CAS GemmArgs& g, int t, float* smem
 template <int KS>
 __device__ __forceinline__ void op_gemm(const CAS GemmArgs& g, int vid, int t, float* smem, unsigned long long* tr) {
   // (ops.h RLE_GEMM_VARIANTS, those of kernel set KS; the host refuses any other id.  PK 4 / 5 take an id
-  // with the norm bit their consumers never set, so their NORM is false)
+  // with the norm bit their consumers never set, so their NORM is false.  KS_ACT dispatches an ELU id a second
+  // time on the op's own activation field: an activation past ACT_TANH runs the variant's kActRt
+  // instantiation, act_f / act_b; PK 0 and 2 only, the engine builds no in-tile prologue for them)
+  constexpr bool XS = ks_family(KS) == KS_EXT;  // (the extended instance or KS_ACT: every variant)
 #define RLE_VX(mode, epi, act, norm, pre, pk, sets)                                                       \
   case gemm_vid(mode, epi, act, norm, pre):                                                               \
-    if constexpr (KS == KS_EXT || (((sets) >> ks_family(KS)) & 1)) {                                     \
+    if constexpr (KS == KS_ACT && mode != GEMM_DW && act == ACT_ELU && ((pk) == 0 || (pk) == 2)) {        \
+      if (art > ACT_TANH) {                                                                               \
+        asm volatile("; gemm variant " #mode " " #epi " kActRt norm " #norm " pk " #pk ::);               \
+        gemm_v<mode, epi, mode != GEMM_DW && act == ACT_ELU ? kActRt : act, (norm) != 0 && (pk) <= 3, pk, \
+               true, wide_variant(mode, epi, pk)>(g, t, smem, tr);                                        \
+        break;                                                                                            \
+      }                                                                                                   \
+    }                                                                                                     \
+    if constexpr (XS || (((sets) >> ks_family(KS)) & 1)) {                                                \
       asm volatile("; gemm variant " #mode " " #epi " " #act " norm " #norm " pk " #pk ::);               \
-      gemm_v<mode, epi, act, (norm) != 0 && (pk) <= 3, pk, KS == KS_EXT || KS == KS_TD7W,                 \
-             (KS == KS_TD7W || KS == KS_EXT) && wide_variant(mode, epi, pk)>(g, t, smem, tr);             \
+      gemm_v<mode, epi, act, (norm) != 0 && (pk) <= 3, pk, XS || KS == KS_TD7W,                           \
+             (KS == KS_TD7W || XS) && wide_variant(mode, epi, pk)>(g, t, smem, tr);                       \
     }                                                                                                     \
     break;
+  [[maybe_unused]] const int art = g.mode == GEMM_FWD ? g.act : g.dact;  // (read by KS_ACT alone)
   switch (vid) {
     RLE_GEMM_VARIANTS(RLE_VX)
     default: break;
@@ -2376,8 +2418,8 @@ __device__ __forceinline__ void op_head_t(const CAS HeadArgs& h, int t, float* s
       for (int n = 0; n < 2; ++n) {
         if (lane == 0 && h.dq[n].t) GW(h.dq[n].t)[tidx(h.dq[n].rbs, b, 0)] = dq[n];
         auto g4 = [&](float4 w, float4 d) {
-          return make_float4((dq[n] * w.x) * act_b<DACT>(d.x), (dq[n] * w.y) * act_b<DACT>(d.y),
-                             (dq[n] * w.z) * act_b<DACT>(d.z), (dq[n] * w.w) * act_b<DACT>(d.w));
+          return make_float4((dq[n] * w.x) * act_b<DACT>(d.x, h.dact), (dq[n] * w.y) * act_b<DACT>(d.y, h.dact),
+                             (dq[n] * w.z) * act_b<DACT>(d.z, h.dact), (dq[n] * w.w) * act_b<DACT>(d.w, h.dact));
         };
         if (in0) mat_str4(h.dz[n], b, c0, g4(wv[n][0], dv[n][0]));
         if (in1) mat_str4(h.dz[n], b, c1, g4(wv[n][1], dv[n][1]));
@@ -2416,8 +2458,11 @@ __device__ __forceinline__ void op_head_t(const CAS HeadArgs& h, int t, float* s
   }
 }
 
-template <bool BC3>
+template <bool BC3, bool RT>  // (RT: KS_ACT -- the activations past ACT_TANH, act_b's run-time slot)
 __device__ __forceinline__ void op_head(const CAS HeadArgs& h, int t, float* smem, unsigned long long* tr) {
+  if constexpr (RT) {
+    if (h.dact > ACT_TANH) return op_head_t<kActRt, BC3>(h, t, smem, tr);
+  }
   if (h.dact == ACT_ELU) op_head_t<ACT_ELU, BC3>(h, t, smem, tr);
   else if (h.dact == ACT_RELU) op_head_t<ACT_RELU, BC3>(h, t, smem, tr);
   else op_head_t<ACT_NONE, BC3>(h, t, smem, tr);
@@ -3215,7 +3260,7 @@ __global__ __launch_bounds__(kThreads, RLE_WAVES) void rle_level(unsigned e0, un
                                                                   const Op* ops_arg, unsigned long long* trace_arg,
                                                                   const Op* next_arg, unsigned next_lines) {
   // 24 KB (the wide instances: the 40 KB LDS ring of gemm_wide)
-  constexpr int kSmemF = (KS == KS_TD7W || KS == KS_EXT) && kWideSmem > 6144 ? kWideSmem : 6144;  // (40 KB)
+  constexpr int kSmemF = (KS == KS_TD7W || ks_family(KS) == KS_EXT) && kWideSmem > 6144 ? kWideSmem : 6144;  // (40 KB)
   static_assert(kSmemF >= kRbOff + 4096, "LDS for the register-blocked exchange");
   __shared__ __attribute__((aligned(16))) float smem[kSmemF];
   // op of this workgroup from the (preloaded) entry table: straight-line selects over SGPRs
@@ -3284,12 +3329,12 @@ __global__ __launch_bounds__(kThreads, RLE_WAVES) void rle_level(unsigned e0, un
     RLE_OP(OP_GEMM, op_gemm<KS>(op.gemm, vid, t, smem, tr))
     RLE_OP(OP_NORMBWD, op_normbwd(op.nb, t))
     RLE_OP(OP_SAMPLE_REDUCE, op_sample_reduce(op.sample, t, smem))
-    RLE_OP(OP_SAMPLE_GATHER, op_sample_gather<KS == KS_EXT>(op.sample, t, smem, tr))
-    RLE_OP(OP_HEAD, op_head<KS == KS_EXT>(op.head, t, smem, tr))
+    RLE_OP(OP_SAMPLE_GATHER, op_sample_gather<ks_family(KS) == KS_EXT>(op.sample, t, smem, tr))
+    RLE_OP(OP_HEAD, (op_head<ks_family(KS) == KS_EXT, KS == KS_ACT>(op.head, t, smem, tr)))
     RLE_OP(OP_PRIORITY, op_priority(op.prio, smem))
     RLE_OP(OP_SAC_ACTOR, op_sac_actor(op.sac, t))
     RLE_OP(OP_SAC_ACTOR_BWD, op_sac_actor_bwd(op.sac, t))
-    RLE_OP(OP_STEP_END, (op_step_end<ks_family(KS) != KS_TD7, KS == KS_EXT>(op.end, smem, tr)))
+    RLE_OP(OP_STEP_END, (op_step_end<ks_family(KS) != KS_TD7, ks_family(KS) == KS_EXT>(op.end, smem, tr)))
     RLE_OP(OP_POLYAK, op_polyak(op.flat, t))
     RLE_OP(OP_COPY, op_copy(op.flat, t))
     RLE_OP(OP_MAXRED, op_maxred(op.flat, t, smem))
@@ -3297,7 +3342,7 @@ __global__ __launch_bounds__(kThreads, RLE_WAVES) void rle_level(unsigned e0, un
     RLE_OP(OP_NOISE, op_noise(op.sample, t))
     RLE_OP(OP_FOLDBIAS, op_foldbias(op.fb))
     // (kinds past 15, ops.h OpKind: low bits 0, kind >> 4 in the variant field; the TD7 family's instances)
-    RLE_OP(0, if (ks_family(KS) != KS_MLP && vid == (OP_BC >> 4)) op_bc<KS == KS_EXT>(op.bc, t, smem))
+    RLE_OP(0, if (ks_family(KS) != KS_MLP && vid == (OP_BC >> 4)) op_bc<ks_family(KS) == KS_EXT>(op.bc, t, smem))
 #undef RLE_OP
     default: break;
   }
@@ -3783,15 +3828,17 @@ int trace_stride() { return kTraceStride; }
 int level_capacity() {
   int per_cu = 0, cus = 0, dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 1024;
-  int p1 = 0, p2 = 0, p3 = 0;  // (every instance: the planner's capacity must hold for the one an engine runs)
+  int p1 = 0, p2 = 0, p3 = 0, p4 = 0;  // (every instance: the planner's capacity must hold for the one an engine runs)
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rle_level<false, KS_TD7>, kThreads, 0) != hipSuccess ||
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&p1, rle_level<false, KS_MLP>, kThreads, 0) != hipSuccess ||
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&p2, rle_level<false, KS_EXT>, kThreads, 0) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&p3, rle_level<false, KS_TD7W>, kThreads, 0) != hipSuccess)
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&p3, rle_level<false, KS_TD7W>, kThreads, 0) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&p4, rle_level<false, KS_ACT>, kThreads, 0) != hipSuccess)
     return 1024;
   per_cu = per_cu < p1 ? per_cu : p1;
   per_cu = per_cu < p2 ? per_cu : p2;
   per_cu = per_cu < p3 ? per_cu : p3;
+  per_cu = per_cu < p4 ? per_cu : p4;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 1024;
   return per_cu * cus;
 }
@@ -3804,6 +3851,7 @@ const char* level_kernel_symbol(int ks) {
   return ks == KS_EXT    ? "_ZN3rle9rle_levelILb0ELi2EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd"
          : ks == KS_MLP  ? "_ZN3rle9rle_levelILb0ELi1EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd"
          : ks == KS_TD7W ? "_ZN3rle9rle_levelILb0ELi3EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd"
+         : ks == KS_ACT  ? "_ZN3rle9rle_levelILb0ELi4EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd"
                          : "_ZN3rle9rle_levelILb0ELi0EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd";
 }
 
@@ -3855,11 +3903,13 @@ hipError_t launch_level(const Op* d_ops, const Op* h_ops, int nops, int nwg, hip
       if (ks == KS_TD7) hipLaunchKernelGGL((rle_level<true, KS_TD7>), grid, dim3(kThreads), 0, st, RLE_LEVEL_ARGS);
       else if (ks == KS_MLP) hipLaunchKernelGGL((rle_level<true, KS_MLP>), grid, dim3(kThreads), 0, st, RLE_LEVEL_ARGS);
       else if (ks == KS_TD7W) hipLaunchKernelGGL((rle_level<true, KS_TD7W>), grid, dim3(kThreads), 0, st, RLE_LEVEL_ARGS);
+      else if (ks == KS_ACT) hipLaunchKernelGGL((rle_level<true, KS_ACT>), grid, dim3(kThreads), 0, st, RLE_LEVEL_ARGS);
       else hipLaunchKernelGGL((rle_level<true, KS_EXT>), grid, dim3(kThreads), 0, st, RLE_LEVEL_ARGS);
     } else {
       if (ks == KS_TD7) hipLaunchKernelGGL((rle_level<false, KS_TD7>), grid, dim3(kThreads), 0, st, RLE_LEVEL_ARGS);
       else if (ks == KS_MLP) hipLaunchKernelGGL((rle_level<false, KS_MLP>), grid, dim3(kThreads), 0, st, RLE_LEVEL_ARGS);
       else if (ks == KS_TD7W) hipLaunchKernelGGL((rle_level<false, KS_TD7W>), grid, dim3(kThreads), 0, st, RLE_LEVEL_ARGS);
+      else if (ks == KS_ACT) hipLaunchKernelGGL((rle_level<false, KS_ACT>), grid, dim3(kThreads), 0, st, RLE_LEVEL_ARGS);
       else hipLaunchKernelGGL((rle_level<false, KS_EXT>), grid, dim3(kThreads), 0, st, RLE_LEVEL_ARGS);
     }
 #undef RLE_LEVEL_ARGS

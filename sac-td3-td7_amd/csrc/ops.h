@@ -83,7 +83,16 @@ struct Operand {
   int pad_[3];
 };
 
-enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_ELU = 2, ACT_TANH = 3 };
+// (ACT_LEAKY: LeakyReLU, negative_slope 0.01; ACT_SILU; ACT_GELU: the exact erf form -- torch's defaults)
+enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_ELU = 2, ACT_TANH = 3, ACT_LEAKY = 4, ACT_SILU = 5, ACT_GELU = 6 };
+// A hidden activation whose layer keeps its pre-activation z and whose derivative is taken from z (as torch's
+// backward does): ELU and the activations past ACT_TANH.  ReLU's is taken from the output, identity has none.
+constexpr bool act_zsaved(int act) { return act == ACT_ELU || act > ACT_TANH; }
+// The activation field of a forward / input-gradient GEMM's variant id (gemm_vid below): its 2 bits hold
+// ACT_NONE .. ACT_TANH, so the activations past ACT_TANH take ELU's id -- ELU's paths do what they need (store z,
+// differentiate from z) -- and the kernel dispatches those ids a second time on GemmArgs::act / dact, in the
+// KS_ACT instance alone (kernels.hip op_gemm, kActRt).
+constexpr int act_vslot(int act) { return act > ACT_TANH ? (int)ACT_ELU : act; }
 
 enum Epi : int {
   EPI_STORE = 0,   // out = act(acc + bias); optional pre-act store, |y| partials, derivative mask, tanh-noise
@@ -209,9 +218,13 @@ constexpr bool wide_variant(int mode, int epi, int pk) {
 // register-blocked weight-gradient tiles and the fused priority sampler)
 // KS_TD7W: the TD7 set with the 64-row LDS-staged tiles (GemmHot::wide) and a larger LDS allocation, for
 // batches >= 512 (rle_plan wide)
-enum KernelSet : int { KS_TD7 = 0, KS_MLP = 1, KS_EXT = 2, KS_TD7W = 3, KS_COUNT = 4 };
+// KS_ACT: the extended instance's code plus the kActRt instantiations of the ELU variants (LeakyReLU / SiLU / GELU,
+// act_vslot above), for engines with one of those activations -- a set of its own, so the extended instance,
+// which the ReLU / ELU / identity combinations outside the agents' own sets run on, is the code it was before
+// those activations existed (their erff / expf epilogues cost its ELU programs 1-2%, DESIGN "More hidden activations")
+enum KernelSet : int { KS_TD7 = 0, KS_MLP = 1, KS_EXT = 2, KS_TD7W = 3, KS_ACT = 4, KS_COUNT = 5 };
 // the agent family whose variants (RLE_GEMM_VARIANTS sets bit) and ops an instance compiles
-constexpr int ks_family(int ks) { return ks == KS_TD7W ? KS_TD7 : ks; }
+constexpr int ks_family(int ks) { return ks == KS_TD7W ? KS_TD7 : ks == KS_ACT ? KS_EXT : ks; }
 
 enum GemmMode : int {
   GEMM_FWD = 0,   // A contiguous (activations), B contiguous (W rows):  Y = X W^T

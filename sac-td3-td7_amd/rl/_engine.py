@@ -61,7 +61,7 @@ def make_config_ext(bc_alpha=0.0) -> ConfigExt:
 
 
 # rle_config act_* codes (include/rle.h RLE_ACT_*): 0 = the reference default of that net
-ACT_CODES = {"default": 0, "relu": 1, "elu": 2, "identity": 3}
+ACT_CODES = {"default": 0, "relu": 1, "elu": 2, "identity": 3, "leaky_relu": 4, "silu": 5, "gelu": 6}
 
 
 class Plan(ctypes.Structure):
@@ -656,7 +656,8 @@ def make_config(algo, state_dim, action_dim, hidden, batch, use_lap=False, disco
                 act_actor="default", act_critic="default", act_encoder="default", bc_lambda=0.0) -> Config:
     """``hidden``: TD7 hdim, TD3 / SAC the width of both hidden layers; ``zs_dim`` (TD7, 0 = hidden) and
     ``hidden_sizes`` (TD3 / SAC: make_mlp's list, 2..6 layers) give the other net shapes (include/rle.h).
-    ``act_*``: hidden activations, "relu" / "elu" / "identity" (make_mlp action_fn=None) or "default".
+    ``act_*``: hidden activations, "relu" / "elu" (alpha 1) / "identity" / "leaky_relu" (slope 0.01) / "silu" /
+    "gelu" (the exact erf form) or "default"; any other name is a ValueError.
     ``bc_lambda`` (TD7): 0 online; > 0 the offline mode's behaviour-cloning weight (rle_config bc_lambda)."""
     hs = list(hidden_sizes) if hidden_sizes is not None else []
     if hs and not 2 <= len(hs) <= 6:

@@ -34,15 +34,22 @@ class _Linears(nn.Module):
 # hidden activations the engine runs (rle_config act_*, include/rle.h RLE_ACT_*), by name
 def _act_name(fn) -> str:
     """A SALE `activ` callable (sale.py:25,67,97) or a make_mlp action_fn module (mlp.py:23) -> "relu" /
-    "elu" / "identity"; NotImplementedError for anything the engine does not run."""
+    "elu" / "identity" / "leaky_relu" / "silu" / "gelu"; NotImplementedError for anything the engine does not
+    run (hidden Tanh, other slopes / alphas, GELU's tanh approximation, functools.partial objects, the rest)."""
     if fn in (F.relu, torch.relu) or isinstance(fn, nn.ReLU):
         return "relu"
     if fn is F.elu or (isinstance(fn, nn.ELU) and fn.alpha == 1.0):
         return "elu"
     if isinstance(fn, nn.Identity):
         return "identity"
-    raise NotImplementedError(f"activation {getattr(fn, '__name__', fn)!r}: the engine runs ReLU, ELU (alpha 1) "
-                              "and Identity")
+    if fn is F.leaky_relu or (isinstance(fn, nn.LeakyReLU) and fn.negative_slope == 0.01):
+        return "leaky_relu"
+    if fn is F.silu or isinstance(fn, nn.SiLU):
+        return "silu"
+    if fn is F.gelu or (isinstance(fn, nn.GELU) and fn.approximate == "none"):
+        return "gelu"
+    raise NotImplementedError(f"activation {getattr(fn, '__name__', fn)!r}: the engine runs ReLU, ELU (alpha 1), "
+                              "Identity, LeakyReLU (slope 0.01), SiLU and GELU (exact)")
 
 
 class SALEEncoder(_Linears):
@@ -147,7 +154,7 @@ def nets_from_make_nn(alg: str, make_nn, state_dim: int, action_dim: int, kwargs
     the engine.  Only this module's classes (the reference's default net types) are accepted, with
     one shape across the agent's nets: (hdim, zs_dim) of the SALE nets, hidden_sizes of the MLPs
     (the shape is {"zs_dim": ...} or {"hidden_sizes": [...]}, as rle_config takes them).  The
-    activations are make_config's act_actor / act_critic / act_encoder ("relu" / "elu" / "identity"):
+    activations are make_config's act_actor / act_critic / act_encoder (the names _act_name returns):
     the SALE nets' `activ`, make_mlp's action_fn; the two critics must agree."""
     import numpy as np
 

@@ -3,6 +3,9 @@ synthetic workload (1M-row replay, random weights).  Not part of the product pat
 "hidden activations".
 
     python tools/acts_bench.py [steps]
+
+A library that refuses a case's activations (RLE_LIB pointing at an older build, for an A/B of the cases both
+run) reports that case as skipped.
 """
 
 import json
@@ -26,6 +29,14 @@ CASES = [
     ("td3", "HalfCheetah-v4", {"act_actor": "elu", "act_critic": "elu"}),
     ("sac", "Humanoid-v4", {}),
     ("sac", "Humanoid-v4", {"act_actor": "elu", "act_critic": "elu"}),
+    # LeakyReLU / SiLU / GELU (DESIGN "More hidden activations"): each in every role of one algorithm
+    ("td7", "Humanoid-v4", {"act_actor": "silu", "act_critic": "gelu", "act_encoder": "leaky_relu"}),
+    ("td7", "Humanoid-v4", {"act_actor": "gelu", "act_critic": "leaky_relu", "act_encoder": "silu"}),
+    ("td7", "Humanoid-v4", {"act_actor": "leaky_relu", "act_critic": "silu", "act_encoder": "gelu"}),
+    ("td3", "HalfCheetah-v4", {"act_actor": "silu", "act_critic": "gelu"}),
+    ("td3", "HalfCheetah-v4", {"act_actor": "leaky_relu", "act_critic": "silu"}),
+    ("sac", "Humanoid-v4", {"act_actor": "gelu", "act_critic": "leaky_relu"}),
+    ("sac", "Humanoid-v4", {"act_actor": "silu", "act_critic": "gelu"}),
 ]
 
 
@@ -33,7 +44,12 @@ def run(alg, env, acts, steps, warmup=100):
     S, A = TASKS[env]
     algo = {"td7": E.RLE_TD7, "td3": E.RLE_TD3, "sac": E.RLE_SAC}[alg]
     lap = alg == "td7"
-    eng = E.Engine(E.make_config(algo, S, A, 256, 256, use_lap=lap, seed=111, **acts))
+    try:
+        eng = E.Engine(E.make_config(algo, S, A, 256, 256, use_lap=lap, seed=111, **acts))
+    except RuntimeError as e:
+        if "activation" not in str(e):
+            raise
+        return {"algo": alg, "env": env, "acts": acts, "skipped": str(e)}
     for net, params in init_agent(alg, S, A, 256, 123).items():
         for name, v in params.items():
             eng.set_param(net, name, v)
