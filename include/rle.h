@@ -137,6 +137,9 @@ typedef struct rle_config_ext {
                                         critics' first layer                                         */
 #define RLE_FUSE_NORMFIN  (1u << 13) /* TD7: the AvgL1Norm row means finalized once (a small op the level after
                                         their producer) for the weight gradients' per-row tables      */
+#define RLE_FUSE_NBROWS   (1u << 14) /* TD7: the deferred AvgL1Norm backward's dot partials stored row-major, so a
+                                        weight-gradient workgroup builds a row's two scalars from 1-5 loads, not 32
+                                        (B <= 256 on the TD7 instance; the same floats either way)   */
 #define RLE_FUSE_OPT_IN RLE_FUSE_PRIOSAMPLE  /* fusions off unless set in fuse_on                      */
 typedef struct rle_plan {
   int level_cap;        /* workgroups per level the tile planner targets (0: resident capacity; TD7 at B >= 1024 5/4

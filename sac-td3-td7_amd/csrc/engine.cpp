@@ -362,6 +362,13 @@ static void gemm_finalize(GemmArgs& g, bool xcd = true) {
   REQUIRE(g.mode != GEMM_DW || (act == kDwGs) == (g.gscale != nullptr), "gemm: gscale is the kDwGs variant's");
   REQUIRE(g.epi != EPI_NBDOT || (g.mode == GEMM_DX && act == ACT_NONE && g.nbx.t && g.norm_out),
           "gemm: EPI_NBDOT is a plain DX with x and partials");
+  // row-major dot partials (RLE_FUSE_NBROWS): 16-row tiles write them; one thread per row reads rs / 4 float4s
+  REQUIRE(g.norm_ld >= 0 || (g.epi == EPI_NBDOT && !g.hot.wide && -g.norm_ld % 4 == 0 && g.tiles_n <= -g.norm_ld),
+          "gemm: row-major partials are the EPI_NBDOT producer's");
+  REQUIRE(!(g.mode == GEMM_DW && act == kDwNb && g.nbdot_ld < 0) ||
+              (g.nbm.nparts == 1 && g.R <= kThreads && -g.nbdot_ld % 4 == 0 && -g.nbdot_ld <= 16 &&
+               g.nbdot_n <= -g.nbdot_ld),
+          "gemm: row-major dot partials need the finalized mean and one row per thread");
   REQUIRE(g.epi != EPI_MSE || act == ACT_NONE, "gemm: MSE epilogue takes no activation");
   REQUIRE((g.dact == ACT_NONE) == (g.dsrc.t == nullptr) || g.mode != GEMM_DX, "gemm: DX derivative source");
   REQUIRE(g.has_pre != 1 || ((g.mode == GEMM_FWD || g.mode == GEMM_DX) && g.prea.N <= 32 && g.prea.seg < g.A.nseg &&
@@ -752,7 +759,12 @@ static void audit_gemm(const GemmArgs& g0) {
           }
           if (g.epi == EPI_QHEAD || g.epi == EPI_QDOT) audit_range(g.qw, h_nblk(g.qw_cbn, 0, j0), 1024, "qw", g);
           if (g.epi == EPI_QHEAD && t == 0) audit_range(g.qb, 0, 4, "qb", g);
-          if (g.norm_out) audit_range(g.norm_out, ((long long)jt * g.norm_ld + i0) * 4, 64, "norm_out", g, 1);
+          if (g.norm_out && g.norm_ld < 0) {  // (row-major partials: one float per row)
+            for (int r = 0; r < 16; ++r)
+              audit_range(g.norm_out, ((long long)(i0 + r) * -g.norm_ld + jt) * 4, 4, "norm_out", g, 1);
+          } else if (g.norm_out) {
+            audit_range(g.norm_out, ((long long)jt * g.norm_ld + i0) * 4, 64, "norm_out", g, 1);
+          }
           if (g.epi == EPI_MSE || g.epi == EPI_QHEAD) audit_range(g.loss_part, (long long)t * 4, 4, "loss_part", g, 1);
         }
       }
@@ -796,7 +808,10 @@ static void audit_gemm(const GemmArgs& g0) {
   }
   if (g.mode == GEMM_DW && g.act == kDwNb) {
     audit_norm(g.nbm, 0, g.R, g);
-    for (int p = 0; p < g.nbdot_n; ++p) audit_range(g.nbdot, (long long)p * g.nbdot_ld * 4, (long long)g.R * 4, "nbdot", g);
+    if (g.nbdot_ld < 0)  // (row-major: every row's whole stride is loaded, kernels.hip nb_rows_issue)
+      audit_range(g.nbdot, 0, (long long)g.R * -g.nbdot_ld * 4, "nbdot", g);
+    else
+      for (int p = 0; p < g.nbdot_n; ++p) audit_range(g.nbdot, (long long)p * g.nbdot_ld * 4, (long long)g.R * 4, "nbdot", g);
   }
 }
 
@@ -2897,11 +2912,17 @@ struct Engine {
               "dx: deferred AvgL1Norm backward operands");
       g.epi = EPI_NBDOT;
       g.nbx = o.nb_x->m;
-      float* part = mem.make<float>((size_t)cdiv(ncols, kTileM) * M);  // any tile plan fits
+      // any tile plan fits (the row stride of the row-major layout: the partial count rounded up to 4)
+      float* part = mem.make<float>((size_t)((cdiv(ncols, kTileM) + 3) & ~3) * M);
+      // RLE_FUSE_NBROWS: row-major partials [row][rs], so the consuming weight gradient's workgroups read a row's
+      // partials in rs / 4 loads (kernels.hip nb_rows_issue: one row per thread, the mean finalized, 16-row tiles)
+      const int rs = (g.tiles_n + 3) & ~3;
+      const bool rows = fused(RLE_FUSE_NBROWS) && fused(RLE_FUSE_NORMFIN) && kernel_set() == KS_TD7 &&
+                        !g.hot.wide && M <= kThreads && rs <= 16;
       g.norm_out = part;
-      g.norm_ld = M;
+      g.norm_ld = rows ? -rs : M;
       out.nbdot = part;
-      out.nbdot_ld = M;
+      out.nbdot_ld = g.norm_ld;
       out.nbdot_n = g.tiles_n;
       out.nbdot_id = next_id++;
       wr.push_back(out.nbdot_id);
@@ -4512,7 +4533,8 @@ struct Engine {
         if (op.kind == OP_GEMM) {
           static const char* kepi[] = {"st", "adam", "mse", "qhead", "nbdot", "act", "qdot", "sacbwd", "sacfwd"};
           static_assert(sizeof(kepi) / sizeof(kepi[0]) == EPI_SACFWD + 1, "every epilogue has a name");
-          const char* ep = op.gemm.mode == GEMM_DW && op.gemm.act == kDwNb ? "adam+nb"
+          // (adam+nbr: the dot partials row-major, RLE_FUSE_NBROWS)
+          const char* ep = op.gemm.mode == GEMM_DW && op.gemm.act == kDwNb ? (op.gemm.nbdot_ld < 0 ? "adam+nbr" : "adam+nb")
                            : op.gemm.mode == GEMM_DW && op.gemm.act == kDwGs ? "adam+gs"
                            : op.gemm.has_pre == 2                         ? "head+dx"
                            : op.gemm.has_pre == 3                         ? (op.gemm.epi == EPI_QDOT ? "qdot+pl" : "st+pl")

@@ -558,10 +558,52 @@ __device__ __forceinline__ void nb_tab_batched(const CAS GemmArgs& g, int n, flo
     }
   }
 }
+// The same tables from row-major dot partials (RLE_FUSE_NBROWS, engine.cpp dx: nbdot_ld = -rs, partial q of row i
+// at nbdot[i * rs + q], rs in {4, 8, 16} and rows past nbdot_n never added; the mean finalized; n <= kThreads):
+// a thread's row is 1 + rs / 4 loads where the batched tables issue 32 clamped ones in every workgroup of the
+// weight gradient.  The floats are nb_tab_batched's: both sums start at 0 and add in partial order.
+// (issue / finish: the DW prologue issues a row's loads ahead of its operand ring and builds the tables while the
+// ring's chunks are in flight -- loads return in order, so behind the ring the tables would wait for all of it)
+struct NbRows {
+  float m0;
+  float4 v[4];
+};
+__device__ __forceinline__ void nb_rows_issue(const CAS GemmArgs& g, int n, NbRows& R) {
+  const int rs = -g.nbdot_ld, i = min((int)threadIdx.x, n - 1);
+  R.m0 = G(g.nbm.part)[g.nbm.row0 + i];
+  const GAS float* p = G(g.nbdot) + (size_t)i * rs;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) R.v[q] = ld4g(p + min(4 * q, rs - 4));
+}
+__device__ __forceinline__ void nb_rows_finish(const CAS GemmArgs& g, int n, const NbRows& R, float* ti, float* tg) {
+  const float xw = (float)(g.nb_width ? g.nb_width : g.nbm.width);
+  const int pd = g.nbdot_n;
+  float sd = 0.f;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (4 * q + 0 < pd) sd += R.v[q].x;
+    if (4 * q + 1 < pd) sd += R.v[q].y;
+    if (4 * q + 2 < pd) sd += R.v[q].z;
+    if (4 * q + 3 < pd) sd += R.v[q].w;
+  }
+  const float mean = (0.f + R.m0) / (float)g.nbm.width, dot = sd / 1.f;
+  const bool clamped = mean < 1e-8f;
+  const float inv = 1.f / (clamped ? 1e-8f : mean);
+  if ((int)threadIdx.x < n) {
+    ti[threadIdx.x] = inv;
+    tg[threadIdx.x] = clamped ? 0.f : (-dot * inv * inv) / xw;
+  }
+}
 __device__ __forceinline__ void build_nb_tab(const CAS GemmArgs& g, int n, float* ti, float* tg) {
   // (x's width: the mean may come finalized, engine.cpp norm_fin, as one partial of width 1)
   const float xw = (float)(g.nb_width ? g.nb_width : g.nbm.width);
   const int pm = g.nbm.nparts, pd = g.nbdot_n;
+  if (g.nbdot_ld < 0) {
+    NbRows R;
+    nb_rows_issue(g, n, R);
+    nb_rows_finish(g, n, R, ti, tg);
+    return;
+  }
   if (n <= kThreads && pm <= 16 && pd <= 16) {
     nb_tab_batched<1, 16, 16>(g, n, ti, tg, xw);
     return;
@@ -1891,13 +1933,38 @@ __device__ __forceinline__ void gemm_v(const CAS GemmArgs& g, int t, float* smem
     const int nrun = run ? c1 - c0 : 0;
     constexpr int RGD = ACT == kDwNb ? kRing : kRingDW;  // (the kDwNb ring carries a third operand)
     float4 ra[RGD], rb[RGD], rx[RGD];
-    ring_issue<RGD>(ra, rb, rsrc(a0p), va, rsrc(sb.p), vb, nrun, bias_tile);
+    bool tabbed = false;
+    int tgo = 0;
     if constexpr (ACT == kDwNb) {
+      tgo = (gR + 15) & ~15;
+      // Row-major dot partials and a whole ring of real loads (wave-uniform): the rows' loads go ahead of the
+      // ring's and the tables are built while the chunks are in flight.  Loads return in order, so behind the
+      // ring the tables wait for every chunk; ahead of it, with a constant number of loads behind them, for the
+      // rows alone.
+      if (g.nbdot_ld < 0 && nrun >= RGD && !bias_tile) {
+        NbRows nr;
+        nb_rows_issue(g, gR, nr);
 #pragma unroll
-      for (int r = 0; r < RGD; ++r)
-        if (r < nrun) rx[r] = bload(rsrc(g.nbx.t), vx + r * 1024);
+        for (int r = 0; r < RGD; ++r) {
+          ra[r] = bload(rsrc(a0p), va + r * 1024);
+          rb[r] = bload(rsrc(sb.p), vb + r * 1024);
+          rx[r] = bload(rsrc(g.nbx.t), vx + r * 1024);
+        }
+        __builtin_amdgcn_sched_barrier(0);  // (the ring's loads stay ahead of the tables' arithmetic)
+        FINE_MARK(0);
+        nb_rows_finish(g, gR, nr, tabs, tabs + tgo);
+        tabbed = true;
+      }
     }
-    FINE_MARK(0);
+    if (!tabbed) {
+      ring_issue<RGD>(ra, rb, rsrc(a0p), va, rsrc(sb.p), vb, nrun, bias_tile);
+      if constexpr (ACT == kDwNb) {
+#pragma unroll
+        for (int r = 0; r < RGD; ++r)
+          if (r < nrun) rx[r] = bload(rsrc(g.nbx.t), vx + r * 1024);
+      }
+      FINE_MARK(0);
+    }
     const float* tb = nullptr;
     if constexpr (NORM) {
       // 1/m of every reduction row of every normed B segment, segment by segment
@@ -1912,10 +1979,8 @@ __device__ __forceinline__ void gemm_v(const CAS GemmArgs& g, int t, float* smem
       __syncthreads();
       if (mine >= 0) tb = tabs + mine + c0 * 16;
     }
-    int tgo = 0;
     if constexpr (ACT == kDwNb) {
-      tgo = (gR + 15) & ~15;
-      build_nb_tab(g, gR, tabs, tabs + tgo);
+      if (!tabbed) build_nb_tab(g, gR, tabs, tabs + tgo);
       __syncthreads();
     }
     FINE_MARK(1);
@@ -2097,8 +2162,10 @@ __device__ __forceinline__ void gemm_v(const CAS GemmArgs& g, int t, float* smem
       for (int q = 0; q < 4; ++q) rd[q] = row16_sum(rd[q]);
       if ((lane & 15) == 0) *(float4*)(red + wave * 16 + ((lane >> 4) << 2)) = make_float4(rd[0], rd[1], rd[2], rd[3]);
       __syncthreads();
+      // (norm_ld < 0: row-major partials [row][-norm_ld] for nb_rows_issue, RLE_FUSE_NBROWS)
       if (tid < 16)
-        GW(g.norm_out)[(size_t)jt * g.norm_ld + i0 + tid] = (red[tid] + red[16 + tid]) + (red[32 + tid] + red[48 + tid]);
+        GW(g.norm_out)[g.norm_ld < 0 ? (size_t)(i0 + tid) * -g.norm_ld + jt : (size_t)jt * g.norm_ld + i0 + tid] =
+            (red[tid] + red[16 + tid]) + (red[32 + tid] + red[48 + tid]);
     };
     epi_nbdot(acc, i0, ib, nbxv, red);
   } else if constexpr (EPI == EPI_ACT) {  // td7.py:141-156 / td3.py:114-129: env action of the act graph

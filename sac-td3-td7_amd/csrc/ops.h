@@ -393,6 +393,9 @@ struct GemmArgs {
   Mat nbx; int nbx_xs;             // EPI_NBDOT / kDwNb: x of the AvgL1Norm (T image; DW: its x-block step)
   NormRef nbm;                     // kDwNb: m of x's rows (producer |x| partials)
   const float* nbdot; int nbdot_ld, nbdot_n;  // kDwNb: the EPI_NBDOT producer's row partials of sum g x
+                                   // (nbdot_ld < 0, and the producer's norm_ld with it: row-major, partial q of
+                                   // row i at [i * -nbdot_ld + q], one row's partials in 1-4 float4 loads;
+                                   // kernels.hip nb_rows_issue, RLE_FUSE_NBROWS)
   int has_pre;                     // 1: pre-GEMM (prea) in use; 2: loss head fused into this DX (hd);
                                    // 3: pre-layer (prea); 4: pre-layer behind a pre-GEMM (prea, prea2;
                                    // variant id: pre 3 with the norm bit, which a pre-layer never sets);
