@@ -406,6 +406,15 @@ int rle_aql_wait_plan(double expected_us, double elapsed_us, double timeout_s, d
  * burst refuses new bursts and completes at once, also for other engines sharing its hardware queue,
  * and no doorbell publishes a run of packets that straddles the ring's end.  0 when every check holds. */
 int rle_aql_selftest(void);
+/* The launch planner alone (no GPU, no HIP or HSA call): the rle_level dispatches of one level of nops ops
+ * -- op q of kind[q], GEMM variant vid[q] (read for GEMM ops only), first workgroup wg_begin[q]; nwg workgroups
+ * in all -- whose op table lies at device address d_ops, followed by a level of next_nops ops at next_ops
+ * (the addresses are copied, never read).  *n: the dispatches, of which at most cap are written to out, 22
+ * dwords each: rle_level's 20-dword argument segment (12 op-table entries; the ops, trace and next-ops
+ * addresses, 2 dwords each; the lines to prefetch; 1 pad), the workgroup count and the kernel instance ks.
+ * *op_bytes: the size of one op descriptor.  A dispatch over the workgroup bound: RLE_EHIP and *n = 0. */
+int rle_level_plan(const int* kind, const int* vid, const int* wg_begin, int nops, int nwg, unsigned long long d_ops,
+                   unsigned long long next_ops, int next_nops, int ks, unsigned* out, int cap, int* n, int* op_bytes);
 /* Copy all weights/optimizer state/counters of src into dst (checkpoint agent,
  * ckpt_agent.load_state_dict(agent), run_w_checkpoint.py:140), and the act path's exploration counter
  * (rle_get_act_counter).  Same algorithm and identical layer shapes required; the batch size may differ. */

@@ -7,10 +7,11 @@
 // sets.  `Prog::schedule` assigns every op the lowest dependency level that
 // respects RAW, WAR and WAW hazards; each level becomes one launch of the
 // device dispatch kernel, and the whole step is captured into a hipGraph.
+//
+// How a captured program reaches the device -- its launch list, the AQL queue (aql_open, aql_submit,
+// aql_wait_step, ...) and struct Graph -- lives in dispatch.cpp / dispatch.h; Error, HIPCHK, REQUIRE and
+// the kernel launchers' prototypes in host.h.
 #include <hip/hip_runtime.h>
-#include <hsa/hsa.h>
-#include <hsa/hsa_ext_amd.h>
-#include <hsa/hsa_ven_amd_loader.h>
 
 #include <algorithm>
 #include <atomic>
@@ -27,53 +28,10 @@
 #include <thread>
 #include <vector>
 
-#include "ops.h"
-#include "rle.h"
+#include "dispatch.h"
 
 namespace rle {
-// next_ops / next_nops: descriptors of the level launched after this one (prefetched into
-// every XCD's L2 during this level; 0: none)
-// ext: the extended kernel instance (register-blocked / 32-row tiles, fused priority sampler)
-hipError_t launch_level(const Op* d_ops, const Op* h_ops, int nops, int nwg, hipStream_t st,
-                        unsigned long long* trace = nullptr, const Op* next_ops = nullptr, int next_nops = 0,
-                        int ks = KS_EXT);
-int level_capacity();
-int trace_stride();
-extern std::vector<LevelLaunch>* g_level_rec;
-const char* level_kernel_symbol(int ks);
-hipError_t launch_append(float* state, float* next_state, float* action, float* reward, float* notdone,
-                         float* priority, const float* st_s, const float* st_ns, const float* st_a,
-                         const float* st_r, const float* st_d, long long ptr, long long cap, int count,
-                         int Sp, int Ap, const float* max_priority, int lap, double* bsum, double* ssum,
-                         long long size_before, hipStream_t st);
-hipError_t launch_act_chain(const ActChainArgs& a, hipStream_t st);
-hipError_t launch_fill(float* state, float* next_state, float* action, float* reward, float* notdone,
-                       float* priority, long long n, int S, int Sp, int A, int Ap, unsigned long long seed,
-                       hipStream_t st);
-hipError_t launch_replay_pack(const ReplayPackArgs& a, hipStream_t st);
-hipError_t launch_replay_unpack(const ReplayPackArgs& a, hipStream_t st);
-hipError_t launch_replay_colsum(const ReplayStatArgs& a, hipStream_t st);
-hipError_t launch_replay_colfin(const ReplayStatArgs& a, hipStream_t st);
-hipError_t launch_replay_normalize(const ReplayNormArgs& a, hipStream_t st);
-hipError_t launch_state_pack(const StatePackArgs& a, hipStream_t st);
-hipError_t launch_state_unpack(const StatePackArgs& a, hipStream_t st);
-
 static thread_local std::string g_err;
-
-struct Error {
-  int code;
-  std::string msg;
-};
-
-#define HIPCHK(x)                                                                               \
-  do {                                                                                          \
-    hipError_t e_ = (x);                                                                        \
-    if (e_ != hipSuccess) throw Error{RLE_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)}; \
-  } while (0)
-#define REQUIRE(c, m)                              \
-  do {                                                \
-    if (!(c)) throw Error{RLE_EINVAL, std::string(m)}; \
-  } while (0)
 
 static inline int r4(int x) { return (x + 3) & ~3; }
 static inline int r16(int x) { return (x + 15) & ~15; }
@@ -1409,305 +1367,6 @@ struct Prog {
   }
 };
 
-// ---- Direct AQL dispatch (default; rle_plan.dispatch 0 for the hipGraph path): the step graphs' level
-// launches written as kernel-dispatch packets into the engine's own HSA queue instead of hipGraph
-// replays.  Fences as HIP's own: agent-scope acquire and release between dependent levels; the first
-// packet of a flush acquires and its last releases at system scope (host-written inputs, host-read
-// results).  tools/mbaql.cpp measured the same packets at 3.83 us per level against hipGraph's 4.08.
-// One HSA queue of a device, shared by the engines aql_open hands it to (at most kAqlQueuesPerDevice
-// per device and process: more user-mode queues than that oversubscribe the device's hardware queue
-// slots, and every queue's dispatches slow down -- profiles/r05_seeds_aql.txt, r05_seeds_hwq.txt).
-// mu: one burst's packets and doorbells at a time (engines driven from several threads).
-struct AqlHw {
-  hsa_agent_t agent{};
-  hsa_queue_t* q = nullptr;
-  uint64_t kobj[KS_COUNT] = {};  // rle_level<false, ks>
-  uint32_t gseg[KS_COUNT] = {}, pseg[KS_COUNT] = {};
-  std::atomic<bool> failed{false};  // a burst on this queue timed out: every engine sharing it fails fast
-  std::mutex mu;
-  ~AqlHw() {
-    if (q) (void)hsa_queue_destroy(q);
-  }
-};
-constexpr int kAqlQueuesPerDevice = 4;
-// An engine's view of its queue: its own completion signal, pending packets and timing.
-struct AqlQueue {
-  std::shared_ptr<AqlHw> hw;
-  hsa_signal_t sig{};
-  struct Pending {
-    const void* ka;
-    unsigned grid;
-    int ks;
-  };
-  std::vector<Pending> pending;
-  // a LOWER bound on the time per packet: the fastest burst seen (>= kAqlMinBurst packets) x kAqlBoundFrac, 0 before
-  // one was timed.  The wait sleeps only through this bound's share of a burst, so it wakes before the burst ends and
-  // spins the rest: a mean-based estimate overslept short bursts (a 20-step bench burst woke 0.5 ms late, -17%).
-  double us_per_launch = 0.0;
-  bool failed = false;          // a flush timed out: its packets may still be queued, the queue takes no more
-  size_t inflight = 0;          // packets submitted since the last aql_complete
-  uint64_t last_idx = 0;        // queue index of the last packet this engine submitted
-  bool timed_idle = false;      // the oldest burst in flight started on an idle queue (its wall time is its own)
-  std::chrono::steady_clock::time_point t0{};  // first doorbell of the oldest burst in flight
-  bool closed() const { return failed || (hw && hw->failed.load(std::memory_order_relaxed)); }
-  ~AqlQueue() {
-    if (sig.handle) (void)hsa_signal_destroy(sig);
-  }
-};
-#define HSACHK(x)                                                                              \
-  do {                                                                                         \
-    hsa_status_t s_ = (x);                                                                     \
-    if (s_ != HSA_STATUS_SUCCESS) throw Error{RLE_EHIP, std::string(#x) + ": hsa status " + std::to_string((int)s_)}; \
-  } while (0)
-
-static hsa_status_t aql_find_gpu(hsa_agent_t a, void* data) {
-  auto* want = static_cast<std::pair<uint32_t, hsa_agent_t>*>(data);
-  hsa_device_type_t t;
-  if (hsa_agent_get_info(a, HSA_AGENT_INFO_DEVICE, &t) != HSA_STATUS_SUCCESS || t != HSA_DEVICE_TYPE_GPU)
-    return HSA_STATUS_SUCCESS;
-  uint32_t bdf = 0;
-  if (hsa_agent_get_info(a, (hsa_agent_info_t)HSA_AMD_AGENT_INFO_BDFID, &bdf) != HSA_STATUS_SUCCESS) return HSA_STATUS_SUCCESS;
-  if (bdf == want->first) {
-    want->second = a;
-    return HSA_STATUS_INFO_BREAK;
-  }
-  return HSA_STATUS_SUCCESS;
-}
-struct AqlFind {
-  hsa_agent_t agent;
-  const char* name;
-  uint64_t kobj;
-  uint32_t gseg, pseg;
-};
-static hsa_status_t aql_find_kernel(hsa_executable_t exe, void* data) {
-  auto* f = static_cast<AqlFind*>(data);
-  hsa_executable_symbol_t sym;
-  if (hsa_executable_get_symbol_by_name(exe, f->name, &f->agent, &sym) == HSA_STATUS_SUCCESS) {
-    hsa_executable_symbol_get_info(sym, HSA_EXECUTABLE_SYMBOL_INFO_KERNEL_OBJECT, &f->kobj);
-    hsa_executable_symbol_get_info(sym, HSA_EXECUTABLE_SYMBOL_INFO_KERNEL_GROUP_SEGMENT_SIZE, &f->gseg);
-    hsa_executable_symbol_get_info(sym, HSA_EXECUTABLE_SYMBOL_INFO_KERNEL_PRIVATE_SEGMENT_SIZE, &f->pseg);
-    return HSA_STATUS_INFO_BREAK;
-  }
-  return HSA_STATUS_SUCCESS;
-}
-
-// The queue of device `dev`, after HIP has loaded librle's code object (any rle_level launch).
-static std::shared_ptr<AqlHw> aql_hw_create(int dev) {
-  auto A = std::make_shared<AqlHw>();
-  HSACHK(hsa_init());
-  hipDeviceProp_t prop;
-  HIPCHK(hipGetDeviceProperties(&prop, dev));
-  std::pair<uint32_t, hsa_agent_t> want{(uint32_t)((prop.pciBusID << 8) | (prop.pciDeviceID << 3)), {}};
-  hsa_iterate_agents(aql_find_gpu, &want);
-  REQUIRE(want.second.handle, "aql: no HSA agent for the HIP device");
-  A->agent = want.second;
-  hsa_ven_amd_loader_1_03_pfn_t tbl;
-  HSACHK(hsa_system_get_major_extension_table(HSA_EXTENSION_AMD_LOADER, 1, sizeof(tbl), &tbl));
-  for (int x = 0; x < KS_COUNT; ++x) {
-    AqlFind f{A->agent, level_kernel_symbol(x), 0, 0, 0};
-    tbl.hsa_ven_amd_loader_iterate_executables(aql_find_kernel, &f);
-    REQUIRE(f.kobj, "aql: rle_level's kernel object is not loaded");
-    A->kobj[x] = f.kobj;
-    A->gseg[x] = f.gseg;
-    A->pseg[x] = f.pseg;
-  }
-  uint32_t qmax = 0;
-  HSACHK(hsa_agent_get_info(A->agent, HSA_AGENT_INFO_QUEUE_MAX_SIZE, &qmax));
-  HSACHK(hsa_queue_create(A->agent, std::min<uint32_t>(qmax, 16384), HSA_QUEUE_TYPE_SINGLE, nullptr, nullptr,
-                          UINT32_MAX, UINT32_MAX, &A->q));
-  return A;
-}
-// The engine's queue: a new HSA queue while the device has fewer than kAqlQueuesPerDevice live ones,
-// else the live one with the fewest engines (its bursts then run in submission order with theirs).
-static std::unique_ptr<AqlQueue> aql_open(int dev) {
-  static std::mutex pool_mu;
-  static std::map<int, std::vector<std::weak_ptr<AqlHw>>> pool;
-  auto A = std::make_unique<AqlQueue>();
-  {
-    std::lock_guard<std::mutex> lk(pool_mu);
-    auto& live = pool[dev];
-    live.erase(std::remove_if(live.begin(), live.end(), [](const std::weak_ptr<AqlHw>& w) { return w.expired(); }),
-               live.end());
-    if ((int)live.size() < kAqlQueuesPerDevice) {
-      A->hw = aql_hw_create(dev);
-      live.push_back(A->hw);
-    } else {
-      for (auto& w : live) {
-        auto h = w.lock();
-        if (h && (!A->hw || h.use_count() < A->hw.use_count())) A->hw = h;
-      }
-    }
-  }
-  HSACHK(hsa_signal_create(0, 0, nullptr, &A->sig));  // (bursts in flight: aql_submit)
-  return A;
-}
-
-// How the host waits for a flush without holding its core (MuJoCo stepping runs on the host cores beside
-// the engine, north_star): while more than kAqlSpinUs of the expected duration remain it sleeps (slices of
-// at most kAqlSliceUs, the signal checked between them), then spins on the signal; past timeout_s it gives
-// up.  expected_us = packets still to retire x a lower bound on the queue's time per packet (AqlQueue::us_per_launch).
-constexpr double kAqlSpinUs = 150.0, kAqlSliceUs = 2000.0, kAqlTimeoutS = 60.0;
-constexpr size_t kAqlMinBurst = 32;   // bursts timed for the per-packet bound (AqlQueue::us_per_launch)
-constexpr double kAqlBoundFrac = 0.92;
-enum AqlWaitAct : int { AQL_SPIN = 0, AQL_SLEEP = 1, AQL_TIMEOUT = 2 };
-static int aql_wait_step(double expected_us, double elapsed_us, double timeout_s, double* sleep_us) {
-  *sleep_us = 0.0;
-  if (elapsed_us > timeout_s * 1e6) return AQL_TIMEOUT;
-  const double left = expected_us - elapsed_us - kAqlSpinUs;
-  if (left < 20.0) return AQL_SPIN;
-  *sleep_us = std::min(left, kAqlSliceUs);
-  return AQL_SLEEP;
-}
-// Waits until pred() holds, by aql_wait_step's policy; on timeout the engine's queue and the shared
-// hardware queue are marked failed (every engine on it then fails fast instead of waiting 60 s again).
-template <class Pred>
-static void aql_wait(AqlQueue& A, Pred pred, double expected_us, const char* what) {
-  const auto t0 = std::chrono::steady_clock::now();
-  while (!pred()) {
-    const double el = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    double sl = 0.0;
-    const int act = aql_wait_step(expected_us, el, kAqlTimeoutS, &sl);
-    if (act == AQL_TIMEOUT) {
-      A.failed = true;
-      if (A.hw) A.hw->failed = true;
-      A.pending.clear();
-      A.inflight = 0;
-      throw Error{RLE_EHIP, std::string("aql: ") + what + " did not complete within 60 s; the engine's queue is "
-                            "closed (every later step fails; destroy the engine)"};
-    }
-    if (act == AQL_SLEEP) std::this_thread::sleep_for(std::chrono::duration<double, std::micro>(sl));
-  }
-}
-static Error aql_closed_error() { return Error{RLE_EHIP, "aql: the engine's queue is closed after a timed-out dispatch"}; }
-
-// Doorbell batching: the doorbell is rung after a packet whose queue index is the last of an aligned
-// group of kAqlDoorbellEvery (and after a burst's last packet).  The groups are aligned to the ABSOLUTE
-// index, so the packets one doorbell publishes never straddle the end of the ring (its size is a power
-// of two >= kAqlDoorbellEvery).  Queue interceptors (rocprofv3's kernel tracing wraps the queue) copy
-// the packets of one doorbell as one contiguous run of the ring: a run that crossed the ring's end read
-// past it (profiles/r05_prof_crash.txt: SIGSEGV at the 1 MB ring's end, 16384 x 64 B).
-constexpr uint64_t kAqlDoorbellEvery = 64;
-static bool aql_doorbell_after(uint64_t idx, bool last) { return last || (idx & (kAqlDoorbellEvery - 1)) == kAqlDoorbellEvery - 1; }
-
-// Writes every pending packet and rings the doorbell; the completion signal counts the submitted bursts
-// still in flight (each burst's last packet decrements it), so bursts may be submitted back to back
-// (rle_step_async) and aql_complete waits for all of them.  A slot is reserved only once the ring has
-// room for it (the wait happens before hsa_queue_add_write_index, under hw.mu, so a timed-out wait never
-// leaves a reserved slot unwritten for the packet processor to stall on).
-static void aql_submit(AqlQueue& A) {
-  const size_t n = A.pending.size();
-  if (!n) return;
-  if (A.closed()) {
-    A.pending.clear();
-    throw aql_closed_error();
-  }
-  AqlHw& hw = *A.hw;
-  std::lock_guard<std::mutex> lk(hw.mu);
-  hsa_queue_t* q = hw.q;
-  const uint64_t mask = q->size - 1;
-  if (!A.inflight) {
-    A.timed_idle = hsa_queue_load_read_index_scacquire(q) == hsa_queue_load_write_index_relaxed(q);
-  }
-  hsa_signal_add_relaxed(A.sig, 1);
-  bool rung = false;
-  uint64_t since_bell = 0;  // packets written since the last doorbell
-  auto bell = [&](uint64_t idx) {
-    hsa_signal_store_screlease(q->doorbell_signal, idx);
-    since_bell = 0;
-    if (!A.inflight && !rung) A.t0 = std::chrono::steady_clock::now();
-    rung = true;
-  };
-  for (size_t i = 0; i < n; ++i) {
-    const uint64_t next = hsa_queue_load_write_index_relaxed(q);
-    if (next - hsa_queue_load_read_index_scacquire(q) >= q->size) {
-      // (bursts of > q->size packets) publish what is written, wait until half the queue has drained, then
-      // write on: the host sleeps through most of it instead of tracking the device one packet at a time
-      if (since_bell) bell(next - 1);
-      const uint64_t half = q->size / 2;
-      const double ahead = (double)(next - hsa_queue_load_read_index_scacquire(q) - half + 1);
-      try {
-        aql_wait(A, [&] { return next - hsa_queue_load_read_index_scacquire(q) < half; }, ahead * A.us_per_launch,
-                 "a queue slot");
-      } catch (...) {
-        hsa_signal_subtract_relaxed(A.sig, 1);  // (this burst's last packet will never be written)
-        throw;
-      }
-    }
-    const uint64_t idx = hsa_queue_add_write_index_relaxed(q, 1);
-    auto* pk = (hsa_kernel_dispatch_packet_t*)q->base_address + (idx & mask);
-    pk->workgroup_size_x = kThreads;
-    pk->workgroup_size_y = 1;
-    pk->workgroup_size_z = 1;
-    pk->reserved0 = 0;
-    pk->grid_size_x = A.pending[i].grid * kThreads;
-    pk->grid_size_y = 1;
-    pk->grid_size_z = 1;
-    const int x = A.pending[i].ks;
-    pk->private_segment_size = hw.pseg[x];
-    pk->group_segment_size = hw.gseg[x];
-    pk->kernel_object = hw.kobj[x];
-    pk->kernarg_address = const_cast<void*>(A.pending[i].ka);
-    pk->reserved2 = 0;
-    const bool last = i + 1 == n;
-    pk->completion_signal = last ? A.sig : hsa_signal_t{0};
-#ifndef RLE_EXP_ACQ  // (timing-only variant builds: make variant-engine; the product uses agent / agent)
-#define RLE_EXP_ACQ HSA_FENCE_SCOPE_AGENT
-#define RLE_EXP_REL HSA_FENCE_SCOPE_AGENT
-#endif
-    const int a = i == 0 ? HSA_FENCE_SCOPE_SYSTEM : RLE_EXP_ACQ;
-    const int r = last ? HSA_FENCE_SCOPE_SYSTEM : RLE_EXP_REL;
-    const uint16_t hdr = (HSA_PACKET_TYPE_KERNEL_DISPATCH << HSA_PACKET_HEADER_TYPE) | (1 << HSA_PACKET_HEADER_BARRIER) |
-                         (a << HSA_PACKET_HEADER_SCACQUIRE_FENCE_SCOPE) | (r << HSA_PACKET_HEADER_SCRELEASE_FENCE_SCOPE);
-    __atomic_store_n((uint32_t*)pk, (uint32_t)hdr | (1u << 16), __ATOMIC_RELEASE);  // header | setup (1 dim)
-    ++since_bell;
-    if (last) A.last_idx = idx;
-    if (aql_doorbell_after(idx, last)) bell(idx);
-  }
-  A.inflight += n;
-  A.pending.clear();
-}
-// Waits until every submitted burst has retired (host-side wall time from the first doorbell of the
-// oldest burst in flight to completion added to *ms when given).  The sleep estimate counts only the
-// packets up to this engine's last one (other engines' later bursts on a pooled queue are not its
-// wait), and the per-packet bound is refreshed only from bursts that started on an idle queue.
-static void aql_complete(AqlQueue& A, double* ms) {
-  if (!A.inflight) return;
-  if (A.closed()) {
-    A.inflight = 0;
-    throw aql_closed_error();
-  }
-  hsa_queue_t* q = A.hw->q;
-  const uint64_t rd = hsa_queue_load_read_index_scacquire(q);
-  const double left = A.last_idx + 1 > rd ? (double)(A.last_idx + 1 - rd) : 0.0;
-  aql_wait(A, [&] { return hsa_signal_load_scacquire(A.sig) < 1; }, left * A.us_per_launch, "a dispatch");
-  const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - A.t0).count();
-  if (A.inflight >= kAqlMinBurst && A.timed_idle) {
-    const double per = kAqlBoundFrac * wall_ms * 1e3 / (double)A.inflight;
-    A.us_per_launch = A.us_per_launch > 0.0 ? std::min(A.us_per_launch, per) : per;
-  }
-  A.inflight = 0;
-  if (ms) *ms += wall_ms;
-}
-static void aql_flush(AqlQueue& A, double* ms) {
-  aql_submit(A);
-  aql_complete(A, ms);
-}
-
-struct Graph {
-  hipGraph_t g = nullptr;
-  hipGraphExec_t x = nullptr;
-  Op* d_ops = nullptr;
-  unsigned long long* trace = nullptr;  // [total wg][4] when RLE_TRACE=1
-  long long trace_n = 0;
-  std::vector<int> nops, nwg, off;
-  std::string desc;
-  int nlaunch = 0;  // rle_level dispatches per replay (a level of > kLevelOps ops takes several)
-  std::vector<std::vector<Op>> host_levels;  // the launches' host op tables (rle_plan dispatch 2)
-  std::vector<LevelLaunch> aql;               // (rle_plan dispatch 1) the dispatches' kernel arguments ...
-  unsigned char* aql_ka = nullptr;            // ... in device memory, 128 B apart
-  int levels() const { return (int)nops.size(); }
-};
-
 struct Layer {
   std::string wname, bname;
   int out = 0, K = 0;
@@ -1871,6 +1530,10 @@ struct Engine {
   int pol_set = 0, pln_set = 0;
   const Graph& policy_graph() const { return g_pol[pol_set]; }
   const Graph& plain_graph() const { return algo == RLE_SAC ? g_pol[pol_set] : g_pln[pln_set]; }  // SAC: every step
+  // rle_graph_describe / rle_graph_trace `which`: 0 policy, 1 plain, 3 the multi-step program, else the hard update
+  const Graph& graph_by(int which) const {
+    return which == 0 ? policy_graph() : which == 1 ? plain_graph() : which == 3 ? g_pair[pol_set] : g_hard;
+  }
   bool built = false;
   long long n_runs = 0;  // host mirror of the agent's step counter
   int cur_set = 0, last_set = 0;       // batch the next step runs on / the last step ran on
@@ -4501,8 +4164,6 @@ struct Engine {
     Graph G;
     size_t total = 0;
     for (auto& lv : levels) {
-      // (launch_level: ceil(ops / kLevelOps) launches)
-      G.nlaunch += (int)((lv.size() + kLevelOps - 1) / kLevelOps);
       G.off.push_back((int)total);
       G.nops.push_back((int)lv.size());
       int wg = 0;
@@ -4573,34 +4234,34 @@ struct Engine {
       for (int w : G.nwg) G.trace_n += w;
       G.trace = mem.make<unsigned long long>((size_t)G.trace_n * trace_stride());
     }
-    if (plan.dispatch == 1 && !G.trace) g_level_rec = &G.aql;
-    HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
     long long tr_off = 0;
     const bool dpf = plan.dpf != 0;  // (rle_plan dpf: the next level's descriptor prefetch workgroups)
     for (size_t l = 0; l < levels.size(); ++l) {
       // (after the last level: this graph's first, as the next replay is usually of the same graph)
       const size_t ln = l + 1 < levels.size() ? l + 1 : 0;
-      hipError_t e = launch_level(G.d_ops + G.off[l], levels[l].data(), G.nops[l], G.nwg[l], stream,
-                                  G.trace ? G.trace + tr_off * trace_stride() : nullptr, G.d_ops + G.off[ln],
-                                  dpf ? G.nops[ln] : 0, kernel_set());
+      level_launches(G.d_ops + G.off[l], levels[l].data(), G.nops[l], G.nwg[l],
+                     G.trace ? G.trace + tr_off * trace_stride() : nullptr, G.d_ops + G.off[ln], dpf ? G.nops[ln] : 0,
+                     kernel_set(), G.launches);
       tr_off += G.nwg[l];
+    }
+    HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+    for (const LevelLaunch& L : G.launches) {
+      const hipError_t e = launch_packet(L, stream);
       if (e != hipSuccess) {
-        g_level_rec = nullptr;
         hipGraph_t tmp;
         (void)hipStreamEndCapture(stream, &tmp);
         throw Error{RLE_EHIP, std::string("launch during capture: ") + hipGetErrorString(e)};
       }
     }
-    g_level_rec = nullptr;
     HIPCHK(hipStreamEndCapture(stream, &G.g));
-    if (!G.aql.empty()) {
-      std::vector<unsigned char> ka(G.aql.size() * 128, 0);
-      for (size_t i = 0; i < G.aql.size(); ++i) std::memcpy(ka.data() + i * 128, G.aql[i].ka, sizeof G.aql[i].ka);
+    if (plan.dispatch == 1 && !G.trace) {  // the AQL packets' kernel arguments
+      std::vector<unsigned char> ka(G.launches.size() * kAqlKaStride, 0);
+      for (size_t i = 0; i < G.launches.size(); ++i)
+        std::memcpy(ka.data() + i * kAqlKaStride, &G.launches[i].ka, sizeof(LevelArgs));
       G.aql_ka = mem.make<unsigned char>(ka.size());
       HIPCHK(hipMemcpy(G.aql_ka, ka.data(), ka.size(), hipMemcpyHostToDevice));
     }
     HIPCHK(hipGraphInstantiate(&G.x, G.g, nullptr, nullptr, 0));
-    G.host_levels = std::move(levels);
     return G;
   }
 
@@ -4823,20 +4484,14 @@ struct Engine {
     if (aql) aql_complete(*aql, ms);
   }
   void launch_graph(const Graph& G) {
-    const bool eager = plan.dispatch == 2;  // (A/B: level launches on the stream, no graph)
-    if (aql_active && !G.aql.empty()) {
-      for (size_t i = 0; i < G.aql.size(); ++i) aql->pending.push_back({G.aql_ka + i * 128, G.aql[i].grid, G.aql[i].ks});
-      launches += G.nlaunch;
-      return;
-    }
-    if (eager && !G.trace) {
-      for (size_t l = 0; l < G.host_levels.size(); ++l)
-        HIPCHK(launch_level(G.d_ops + G.off[l], G.host_levels[l].data(), G.nops[l], G.nwg[l], stream, nullptr,
-                            nullptr, 0, kernel_set()));
+    if (aql_active && G.aql_ka) {
+      aql->pending.push_back({&G.launches, G.aql_ka});
+    } else if (plan.dispatch == 2 && !G.trace) {  // (A/B: the launches on the stream, no graph)
+      for (const LevelLaunch& L : G.launches) HIPCHK(launch_packet(L, stream));
     } else {
       HIPCHK(hipGraphLaunch(G.x, stream));
     }
-    launches += G.nlaunch;
+    launches += G.nlaunch();
   }
   // The next K steps (multi_k, or a remainder program's) may run as one multi-step program: TD7 (counter
   // bumped first, td7.py:295) / TD3 (td3.py:231) when its first step is a policy step (and, TD7, no step
@@ -4876,7 +4531,7 @@ struct Engine {
     // direct dispatch (rle_plan dispatch 1): the graphs' levels go to the engine's own queue; the HIP
     // stream is drained first and the queue after each chunk (host-side ordering between them; async:
     // the last chunk stays in flight, aql_drain)
-    const bool use_aql = aql_mode() && !g_pol[0].aql.empty();
+    const bool use_aql = aql_mode() && g_pol[0].aql_ka;
     if (use_aql && !aql) aql = aql_open(cfg.device);
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (gpu_ms && !use_aql) {  // (AQL: the levels run outside the stream; host wall time instead)
@@ -4893,7 +4548,7 @@ struct Engine {
         HIPCHK(hipStreamSynchronize(stream));
         aql_active = true;
         launch_graph(g_slot0);
-        launches -= g_slot0.nlaunch;  // (not a step level)
+        launches -= g_slot0.nlaunch();  // (not a step level)
       } else {
         int zero = 0;
         HIPCHK(hipMemcpyAsync(&ctrl->info_slot, &zero, sizeof(int), hipMemcpyHostToDevice, stream));
@@ -6155,10 +5810,7 @@ int rle_graph_describe(rle_engine* h, int which, char* buf, int len) {
   return guard([&] {
     Engine& e = drained(h);
     if (!e.built) e.build();
-    const rle::Graph& G = which == 0 ? e.policy_graph()
-                          : which == 1 ? e.plain_graph()
-                          : which == 3 ? e.g_pair[e.pol_set]
-                                       : e.g_hard;
+    const rle::Graph& G = e.graph_by(which);
     REQUIRE(buf && len > 0, "describe: bad buffer");
     std::snprintf(buf, (size_t)len, "%s", G.desc.c_str());
   });
@@ -6169,10 +5821,7 @@ int rle_graph_trace(rle_engine* h, int which, unsigned long long* out, long long
     Engine& e = drained(h);
     REQUIRE(n_out, "trace: null n_out");
     if (!e.built) e.build();
-    const rle::Graph& G = which == 0 ? e.policy_graph()
-                          : which == 1 ? e.plain_graph()
-                          : which == 3 ? e.g_pair[e.pol_set]
-                                       : e.g_hard;
+    const rle::Graph& G = e.graph_by(which);
     *n_out = G.trace ? G.trace_n : 0;
     if (!G.trace || !out) return;
     const int st = rle::trace_stride();
@@ -6189,52 +5838,32 @@ int rle_trace_stride(void) { return rle::trace_stride(); }
 // queue refuses new bursts and completes at once, for the engine that timed out and for every engine
 // sharing its hardware queue; doorbell groups never straddle the ring's end.
 int rle_aql_selftest(void) {
+  return guard([&] { rle::aql_selftest(); });
+}
+
+// The launch planner on a level made up from the three fields it reads of each op (no device: the table
+// addresses are only copied into the packets).
+int rle_level_plan(const int* kind, const int* vid, const int* wg_begin, int nops, int nwg, unsigned long long d_ops,
+                   unsigned long long next_ops, int next_nops, int ks, unsigned* out, int cap, int* n, int* op_bytes) {
   return guard([&] {
-    using namespace rle;
-    auto hw = std::make_shared<AqlHw>();
-    AqlQueue a, b;
-    a.hw = hw;
-    b.hw = hw;
-    REQUIRE(!a.closed() && !b.closed(), "selftest: fresh queues closed");
-    a.failed = true;
-    hw->failed = true;  // (as aql_wait's timeout leaves them)
-    a.pending.push_back({nullptr, 1, 0});
-    a.inflight = 7;
-    int refused = 0;
-    try {
-      aql_submit(a);
-    } catch (const Error&) {
-      ++refused;
+    REQUIRE(kind && vid && wg_begin && nops > 0 && n && cap >= 0 && (out || cap == 0), "level_plan: bad args");
+    *n = 0;
+    if (op_bytes) *op_bytes = (int)sizeof(rle::Op);
+    std::vector<rle::Op> ops((size_t)nops);
+    for (int q = 0; q < nops; ++q) {
+      ops[q].kind = kind[q];
+      ops[q].wg_begin = wg_begin[q];
+      if (kind[q] == rle::OP_GEMM) ops[q].gemm.vid = vid[q];
     }
-    REQUIRE(refused == 1 && a.pending.empty(), "selftest: a closed queue took a burst");
-    try {
-      aql_complete(a, nullptr);
-    } catch (const Error&) {
-      ++refused;
+    std::vector<rle::LevelLaunch> L;
+    rle::level_launches(reinterpret_cast<const rle::Op*>(d_ops), ops.data(), nops, nwg, nullptr,
+                        reinterpret_cast<const rle::Op*>(next_ops), next_nops, ks, L);
+    *n = (int)L.size();
+    for (int i = 0; i < *n && i < cap; ++i) {
+      std::memcpy(out + 22 * i, &L[i].ka, sizeof(rle::LevelArgs));
+      out[22 * i + 20] = L[i].grid;
+      out[22 * i + 21] = (unsigned)L[i].ks;
     }
-    REQUIRE(refused == 2 && a.inflight == 0, "selftest: a closed queue waited for its burst");
-    aql_complete(a, nullptr);  // (nothing in flight: returns)
-    b.pending.push_back({nullptr, 1, 0});
-    try {
-      aql_submit(b);
-    } catch (const Error&) {
-      ++refused;
-    }
-    REQUIRE(refused == 3, "selftest: an engine sharing a failed hardware queue took a burst");
-    // doorbell groups: for every start index, the packets between two doorbells lie in one pass of the ring
-    for (uint64_t size : {64ull, 1024ull, 16384ull})
-      for (uint64_t start = size - 130; start < size + 130; ++start)
-        for (uint64_t n : {1ull, 5ull, 64ull, 200ull}) {
-          uint64_t first = start;
-          for (uint64_t i = start; i < start + n; ++i)
-            if (aql_doorbell_after(i, i + 1 == start + n)) {
-              REQUIRE(first / size == i / size, "selftest: a doorbell group straddles the ring's end");
-              first = i + 1;
-            }
-          REQUIRE(first == start + n, "selftest: packets left without a doorbell");
-        }
-    a.hw.reset();
-    b.hw.reset();
   });
 }
 

@@ -28,9 +28,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include <cstring>
 #include <type_traits>
-#include <vector>
 
 #include "ops.h"
 
@@ -3888,102 +3886,67 @@ __global__ __launch_bounds__(kThreads) void rle_state_unpack(const StatePackArgs
 
 // ---------------------------------------------------------------- host launchers
 
-// Workgroups of rle_level resident at once on the current device.
 // Timestamps per workgroup in trace buffers (4; 16 in -DRLE_TRACE_FINE builds).
 int trace_stride() { return kTraceStride; }
 
+// The rle_level instances: one row per KernelSet (ops.h), in the enum's order, with the HSA symbol name of
+// the row's production kernel (AQL dispatch).  kLevel is the rows turned into columns -- the production
+// kernels, then the traced ones, then the names -- so that the instances are emitted in that order.
+#define RLE_LEVEL_INSTANCES(X)                                             \
+  X(KS_TD7, "_ZN3rle9rle_levelILb0ELi0EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd")  \
+  X(KS_MLP, "_ZN3rle9rle_levelILb0ELi1EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd")  \
+  X(KS_EXT, "_ZN3rle9rle_levelILb0ELi2EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd")  \
+  X(KS_TD7W, "_ZN3rle9rle_levelILb0ELi3EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd") \
+  X(KS_ACT, "_ZN3rle9rle_levelILb0ELi4EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd")
+#define RLE_ROW_KS(KS, sym) KS,
+#define RLE_ROW_FN(KS, sym) (const void*)rle_level<false, KS>,
+#define RLE_ROW_FN_TRACED(KS, sym) (const void*)rle_level<true, KS>,
+#define RLE_ROW_SYMBOL(KS, sym) sym,
+static const struct {
+  const void* fn[2][KS_COUNT];  // [traced][ks]
+  const char* symbol[KS_COUNT];
+} kLevel = {{{RLE_LEVEL_INSTANCES(RLE_ROW_FN)}, {RLE_LEVEL_INSTANCES(RLE_ROW_FN_TRACED)}},
+            {RLE_LEVEL_INSTANCES(RLE_ROW_SYMBOL)}};
+constexpr int kLevelRowKs[] = {RLE_LEVEL_INSTANCES(RLE_ROW_KS)};
+constexpr bool level_rows_follow_enum() {
+  for (int i = 0; i < KS_COUNT; ++i)
+    if (kLevelRowKs[i] != i) return false;
+  return true;
+}
+static_assert(sizeof(kLevelRowKs) == KS_COUNT * sizeof(int) && level_rows_follow_enum(),
+              "RLE_LEVEL_INSTANCES: one row per KernelSet, in the enum's order");
+#undef RLE_ROW_KS
+#undef RLE_ROW_FN
+#undef RLE_ROW_FN_TRACED
+#undef RLE_ROW_SYMBOL
+
+// Workgroups of rle_level resident at once on the current device (the least over the instances: the
+// planner's capacity must hold for the one an engine runs).
 int level_capacity() {
-  int per_cu = 0, cus = 0, dev = 0;
+  int per_cu = 1 << 30, cus = 0, dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 1024;
-  int p1 = 0, p2 = 0, p3 = 0, p4 = 0;  // (every instance: the planner's capacity must hold for the one an engine runs)
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rle_level<false, KS_TD7>, kThreads, 0) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&p1, rle_level<false, KS_MLP>, kThreads, 0) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&p2, rle_level<false, KS_EXT>, kThreads, 0) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&p3, rle_level<false, KS_TD7W>, kThreads, 0) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&p4, rle_level<false, KS_ACT>, kThreads, 0) != hipSuccess)
-    return 1024;
-  per_cu = per_cu < p1 ? per_cu : p1;
-  per_cu = per_cu < p2 ? per_cu : p2;
-  per_cu = per_cu < p3 ? per_cu : p3;
-  per_cu = per_cu < p4 ? per_cu : p4;
+  for (const void* fn : kLevel.fn[0]) {
+    int p = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&p, fn, kThreads, 0) != hipSuccess) return 1024;
+    per_cu = per_cu < p ? per_cu : p;
+  }
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 1024;
   return per_cu * cus;
 }
 
-// (host) when set, launch_level also appends each dispatch's kernel arguments here (capture of the
-// AQL launch lists; traced launches are never recorded)
-std::vector<LevelLaunch>* g_level_rec = nullptr;
-// the production kernel's HSA symbol name (AQL dispatch)
-const char* level_kernel_symbol(int ks) {
-  return ks == KS_EXT    ? "_ZN3rle9rle_levelILb0ELi2EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd"
-         : ks == KS_MLP  ? "_ZN3rle9rle_levelILb0ELi1EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd"
-         : ks == KS_TD7W ? "_ZN3rle9rle_levelILb0ELi3EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd"
-         : ks == KS_ACT  ? "_ZN3rle9rle_levelILb0ELi4EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd"
-                         : "_ZN3rle9rle_levelILb0ELi0EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd";
-}
+const char* level_kernel_symbol(int ks) { return kLevel.symbol[ks]; }
 
-hipError_t launch_level(const Op* d_ops, const Op* h_ops, int nops, int nwg, hipStream_t st,
-                        unsigned long long* trace, const Op* next_ops, int next_nops, int ks) {
-  // a level of more than kLevelOps ops: consecutive launches of kLevelOps (its ops are
-  // independent, so any split is correct)
-  for (int q0 = 0; q0 < nops; q0 += kLevelOps) {
-    const int n = nops - q0 < kLevelOps ? nops - q0 : kLevelOps;
-    const int w0 = h_ops[q0].wg_begin;
-    const int w1 = q0 + n < nops ? h_ops[q0 + n].wg_begin : nwg;
-    if (w1 - w0 + 8 > kMaxLevelWG) return hipErrorInvalidValue;
-    LevelArgs la{};
-    la.ops = d_ops + q0;
-    la.trace = trace ? trace + (size_t)w0 * kTraceStride : nullptr;
-    // the following launch's ops: the rest of this level, then the next level's
-    const bool last = q0 + n >= nops;
-    const int nn = !last ? (nops - q0 - n < kLevelOps ? nops - q0 - n : kLevelOps)
-                         : (next_nops <= kLevelOps ? next_nops : kLevelOps);
-    const Op* next = !last ? d_ops + q0 + n : next_ops;
-    const unsigned next_lines = (unsigned)(nn * (int)(sizeof(Op) / 64) < 2 * kThreads ? nn * (int)(sizeof(Op) / 64) : 2 * kThreads);
-    const int npf = next_lines ? 8 : 0;  // leading prefetch workgroups (entry 0 bit 31)
-    for (int q = 0; q < kLevelOps; ++q) {
-      if (q < n) {
-        const Op& o = h_ops[q0 + q];
-        const unsigned vid = o.kind == OP_GEMM ? (unsigned)o.gemm.vid : (unsigned)o.kind >> 4;
-        la.entry[q] = (unsigned)(o.wg_begin - w0) | (((unsigned)o.kind & 0xfu) << 16) | (vid << 20);
-      } else {
-        la.entry[q] = 0xffffu;
-      }
-    }
-    if (npf) la.entry[0] |= 0x80000000u;
-    if (g_level_rec && !trace) {  // (traced launches are never recorded)
-      LevelLaunch L{};
-      std::memcpy(L.ka, la.entry, sizeof la.entry);
-      std::memcpy(L.ka + 48, &la.ops, 8);
-      std::memcpy(L.ka + 56, &la.trace, 8);
-      std::memcpy(L.ka + 64, &next, 8);
-      std::memcpy(L.ka + 72, &next_lines, 4);
-      L.grid = (unsigned)(w1 - w0 + npf);
-      L.ks = ks;
-      g_level_rec->push_back(L);
-    }
-#define RLE_LEVEL_ARGS                                                                                         \
-  la.entry[0], la.entry[1], la.entry[2], la.entry[3], la.entry[4], la.entry[5], la.entry[6], la.entry[7], \
-      la.entry[8], la.entry[9], la.entry[10], la.entry[11], la.ops, la.trace, next, next_lines
-    const dim3 grid(w1 - w0 + npf);
-    if (trace) {
-      if (ks == KS_TD7) hipLaunchKernelGGL((rle_level<true, KS_TD7>), grid, dim3(kThreads), 0, st, RLE_LEVEL_ARGS);
-      else if (ks == KS_MLP) hipLaunchKernelGGL((rle_level<true, KS_MLP>), grid, dim3(kThreads), 0, st, RLE_LEVEL_ARGS);
-      else if (ks == KS_TD7W) hipLaunchKernelGGL((rle_level<true, KS_TD7W>), grid, dim3(kThreads), 0, st, RLE_LEVEL_ARGS);
-      else if (ks == KS_ACT) hipLaunchKernelGGL((rle_level<true, KS_ACT>), grid, dim3(kThreads), 0, st, RLE_LEVEL_ARGS);
-      else hipLaunchKernelGGL((rle_level<true, KS_EXT>), grid, dim3(kThreads), 0, st, RLE_LEVEL_ARGS);
-    } else {
-      if (ks == KS_TD7) hipLaunchKernelGGL((rle_level<false, KS_TD7>), grid, dim3(kThreads), 0, st, RLE_LEVEL_ARGS);
-      else if (ks == KS_MLP) hipLaunchKernelGGL((rle_level<false, KS_MLP>), grid, dim3(kThreads), 0, st, RLE_LEVEL_ARGS);
-      else if (ks == KS_TD7W) hipLaunchKernelGGL((rle_level<false, KS_TD7W>), grid, dim3(kThreads), 0, st, RLE_LEVEL_ARGS);
-      else if (ks == KS_ACT) hipLaunchKernelGGL((rle_level<false, KS_ACT>), grid, dim3(kThreads), 0, st, RLE_LEVEL_ARGS);
-      else hipLaunchKernelGGL((rle_level<false, KS_EXT>), grid, dim3(kThreads), 0, st, RLE_LEVEL_ARGS);
-    }
-#undef RLE_LEVEL_ARGS
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+// Launches the instance the packet names with the packet's own argument bytes.
+hipError_t launch_packet(const LevelLaunch& L, hipStream_t st) {
+  if (L.ks < 0 || L.ks >= KS_COUNT) return hipErrorInvalidValue;
+  LevelArgs ka = L.ka;
+  void* args[kLevelOps + 4];
+  for (int q = 0; q < kLevelOps; ++q) args[q] = &ka.entry[q];
+  args[kLevelOps] = &ka.ops;
+  args[kLevelOps + 1] = &ka.trace;
+  args[kLevelOps + 2] = &ka.next;
+  args[kLevelOps + 3] = &ka.next_lines;
+  return hipLaunchKernel(kLevel.fn[L.traced][L.ks], dim3(L.grid), dim3(kThreads), args, 0, st);
 }
 hipError_t launch_append(float* state, float* next_state, float* action, float* reward, float* notdone,
                          float* priority, const float* st_s, const float* st_ns, const float* st_a,

@@ -682,26 +682,34 @@ struct ActChainArgs {
   float obs[384];      // the observation (padded, zeros)
 };
 
-// Kernel argument of one level launch: the workgroup -> op table travels in the
-// kernarg segment (one scalar load burst) instead of being searched in memory.
+// Kernel arguments of one level launch, laid out as rle_level's argument segment (76 bytes, no hidden
+// arguments): the workgroup -> op table travels in the kernarg segment (one scalar load burst) instead
+// of being searched in memory.
 constexpr int kLevelOps = 12;  // ops per launch: the op table is 12 preloaded kernel arguments
 struct LevelArgs {
-  const Op* ops;
-  unsigned long long* trace;  // optional phase timestamps [wg][4] (s_memrealtime, 100 MHz)
   // op q: first workgroup (bits 0-15; 0xffff past the last op) | (kind & 15) << 16 | GEMM
   // variant id << 20 (GemmArgs::vid: the variant is chosen before any descriptor load; a non-GEMM
-  // op: kind >> 4, 0 for every kind up to 15)
+  // op: kind >> 4, 0 for every kind up to 15).  Entry 0 bit 31: the launch leads with 8 workgroups
+  // that load `next_lines` 64-byte lines from `next` into every XCD's L2.
   unsigned entry[kLevelOps];
+  const Op* ops;
+  unsigned long long* trace;  // optional phase timestamps [wg][4] (s_memrealtime, 100 MHz)
+  const Op* next;             // the ops of the launch after this one
+  unsigned next_lines;        // at most 2 * kThreads
 };
+static_assert(offsetof(LevelArgs, ops) == 48 && offsetof(LevelArgs, trace) == 56 && offsetof(LevelArgs, next) == 64 &&
+                  offsetof(LevelArgs, next_lines) == 72 && sizeof(LevelArgs) == 80,
+              "LevelArgs is rle_level's kernel-argument segment");
 constexpr int kMaxLevelWG = 0xfffe;  // workgroups per launch (16-bit entry field)
 
-// One rle_level dispatch as an AQL packet needs it (engine.cpp direct dispatch, rle_plan.dispatch 1): the
-// kernel-argument bytes (rle_level<false>'s 76-byte segment: no hidden arguments) and the
-// workgroup count.  launch_level appends one per dispatch while g_level_rec is set.
+// One rle_level dispatch, as dispatch.cpp level_launches plans it and as every launch path consumes it
+// (stream capture, launches on the stream, AQL packets): the kernel arguments, the workgroup count and
+// the kernel.
 struct LevelLaunch {
-  unsigned char ka[80];
-  unsigned grid;  // workgroups
+  LevelArgs ka;
+  unsigned grid;  // workgroups (the prefetch workgroups included)
   int ks;         // the rle_level instance (KernelSet)
+  bool traced;    // rle_level<true, ks> (RLE_TRACE=1 programs; never an AQL packet)
 };
 
 // Device control block.

@@ -207,6 +207,9 @@ SIGNATURES = {
     "rle_trace_stride": (_int, []),
     "rle_aql_wait_plan": (_int, [ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
     "rle_aql_selftest": (_int, []),
+    "rle_level_plan": (_int, [ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int), _int, _int,
+                              ctypes.c_ulonglong, ctypes.c_ulonglong, _int, _int, ctypes.POINTER(ctypes.c_uint), _int,
+                              ctypes.POINTER(_int), ctypes.POINTER(_int)]),
     "rle_eval": (_int, [_vp, _int, _cs, _cs, _f32p, _f32p, _int, _f32p]),
     "rle_sac_rsample": (_int, [_vp, _f32p, _f32p, _f32p, _int, _f32p, _f32p]),
     "rle_get_info": (_int, [_vp, _int, _f32p]),

@@ -8,7 +8,8 @@ NAME: a golden of tests/golden, edge:<case> for a case of tests/edge_cases.py (b
 as tests/test_shape_edges_gpu.py builds it), or offline3:<shape> for an offline TD3 (TD3+BC) engine over a shape
 of tests/test_offline_td3_gpu.py's SHAPES (its _env, offline_engine, ALPHA and tapes: OP_BC modes 2 and 3 and the
 kDwGs weight gradients, which no golden or edge case builds).  Per step: every parameter, the priorities and the
-info row after a single-step replay.  The dump also holds the programs' descriptions (rle_graph_describe 0, 1, 3
+info row after a single-step replay, and the engine's launch count (launches_<t>: how many rle_level dispatches
+the programs replayed so far took).  The dump also holds the programs' descriptions (rle_graph_describe 0, 1, 3
 and the hard-update program; empty where the engine has none) -- with RLE_DESC_WG=1 in the environment
 they carry every op's workgroup count, so a changed tile plan shows even where the floats agree.
 
@@ -96,6 +97,7 @@ def dump(name, steps, out):
     burst = int(os.environ.get("BITCMP_BURST", "1"))  # steps per rle_step call (6: TD7's multi-step graphs)
     for t in range(0, steps, burst):
         res[f"info_{t}"] = np.asarray(eng.step(min(burst, steps - t)))
+        res[f"launches_{t}"] = np.array(eng.launch_count(), np.int64)
         if use_lap:
             res[f"prio_{t}"] = rep.get_priority(Ncap)
         for net, ps in shapes.items():
