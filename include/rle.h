@@ -99,8 +99,26 @@ typedef struct rle_config_ext {
      with the standalone loss head).  The info row gains train/bc (the mse)
      and train/lmbda after norm/policy (NaN on other steps).  The parameter layout does not change:
      rle_copy_state, rle_copy_nets and rle_state_* work between engines whose bc_alpha differ.  Negative, NaN,
-     infinite, > 0 with another algorithm, or a `size` that does not reach the field: RLE_EINVAL. */
+     infinite, > 0 with another algorithm, or a `size` that does not reach the field (see awac_lambda for the
+     valid sizes): RLE_EINVAL. */
   float bc_alpha;
+  /* SAC offline mode (AWAC, Nair et al. 2020; the reference does not implement it): the critic step is SAC's own
+     at a fixed temperature of 0, and the policy step minimises
+       L = -mean(w log pi(a | s)),   w = min(exp((Q(s, a) - Q(s, a_pi)) / awac_lambda), 100).detach()
+     (a: the batch's stored action, clamped to +-(1 - 1e-6) before atanh; a_pi: the policy's own rsample;
+     Q = min(Q1, Q2) of the updated critics; log pi: the squashed Gaussian's, with annotation.py:12 EPS; every mean
+     over the B valid rows; no guard for a tiny sigma).  0 = online: the programs are the online ones, op for op.
+     > 0 (the paper: 1): requires algo == RLE_SAC, tmp == 0 and use_lap == 0.  No gradient passes through the
+     critics: the policy phase forwards them on (s, a) and (s, a_pi), one row-wise op (OP_AWAC) forms adv, w and
+     dL / d(mean | log_std), and the actor's backward and Adam run from there as online; the critics' input
+     gradients, the squashed-Gaussian backward, the policy loss head and the temperature update are absent.  A step
+     has no more levels than online.  The info row is train/q_fn, train/policy (= L), entropy, train/adv (mean
+     advantage) and train/weight (mean w).  The parameter layout is that of a fixed-temperature SAC engine:
+     rle_copy_state, rle_copy_nets and rle_state_* work between engines whose awac_lambda differ.  Negative, NaN,
+     infinite, > 0 with another algorithm, with tmp != 0 or with use_lap: RLE_EINVAL.
+     `size`: one of the sizes this struct ever had, 8 (through bc_alpha) or 12 (through awac_lambda); any other
+     value, one that ends inside a field included, is RLE_EINVAL. */
+  float awac_lambda;
 } rle_config_ext;
 #define RLE_MAX_HIDDEN 6
 #define RLE_ACT_DEFAULT 0

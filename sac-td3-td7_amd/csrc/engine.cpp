@@ -1002,6 +1002,21 @@ static void op_accesses(const Op& op, std::vector<Access>& v) {
       acc_bytes(v, b.out, 4, 1, "bc q_abs");
       break;
     }
+    case OP_AWAC: {  // (rows < nvalid of every operand; whole images where a row's floats are scattered)
+      const AwacArgs& a = op.awac;
+      acc_mat(v, a.raw, 0, "awac raw");
+      acc_mat(v, a.a, 0, "awac a");
+      for (int n = 0; n < 2; ++n) {
+        acc_mat(v, a.qd[n], 0, "awac q(s, a)");
+        acc_mat(v, a.qv[n], 0, "awac q(s, a_pi)");
+      }
+      acc_bytes(v, a.logpi, (long long)a.nvalid * 4, 0, "awac logpi");
+      acc_mat(v, a.dout, 1, "awac dout");
+      acc_bytes(v, a.adv, (long long)a.nvalid * 4, 1, "awac adv");
+      acc_bytes(v, a.w, (long long)a.nvalid * 4, 1, "awac w");
+      acc_bytes(v, a.part, (long long)((a.nvalid + 3) / 4) * 16, 1, "awac partials");
+      break;
+    }
     case OP_FOLDBIAS: {
       const FoldBiasArgs& f = op.fb;
       acc_bytes(v, f.wn, (long long)((f.H + 15) / 16) * f.cbn * 1024, 0, "fold w");
@@ -1427,6 +1442,7 @@ struct Engine {
     // (offline TD3: OP_BC modes 2 / 3, the kDwGs variant, the |min| slot and the info kinds are the extended
     // instance's alone, so the TD3 / SAC instance is byte for byte what the online programs ran on before)
     if (offline3()) return KS_EXT;
+    if (offline_sac()) return KS_EXT;  // (OP_AWAC is the extended instance's alone, for the same reason)
     if (algo == RLE_TD7 && plan.wide && !(plan.fuse_on & RLE_FUSE_PRIOSAMPLE)) return KS_TD7W;  // (rb compiled in)
     if (plan.rb || (plan.fuse_on & RLE_FUSE_PRIOSAMPLE) || plan.wide) return KS_EXT;
     return algo == RLE_TD7 ? KS_TD7 : KS_MLP;
@@ -3304,6 +3320,9 @@ struct Engine {
   bool offline() const { return algo == RLE_TD7 && cfg.bc_lambda > 0.f; }
   float bc_alpha = 0.f;
   bool offline3() const { return algo == RLE_TD3 && bc_alpha > 0.f; }
+  // offline SAC (rle_config_ext awac_lambda > 0, AWAC; the temperature is fixed at 0)
+  float awac_lambda = 0.f;
+  bool offline_sac() const { return algo == RLE_SAC && awac_lambda > 0.f; }
 
   // ---- TD7 (td7.py:287-332): build_td7 below is the list of these phases.
   // Encoder update (td7.py:246-257): the online encoder on [s; s'] (one GEMM per layer), zsa3 with the MSE
@@ -3907,12 +3926,10 @@ struct Engine {
   void mlp_policy(Prog& pg, StepBuild& sb, const MlpActor& ac) {
     const bool sac = algo == RLE_SAC;
     const int D = (int)HS.size();
-    Net& pi = net("policy");
     Net* q[2] = {&net("q1"), &net("q2")};
-    const Layer& Lout = pi.layers[D];
     const Layer* qo[2] = {&q[0]->layers[D], &q[1]->layers[D]};
     const View &s = sb.s, &a_pi = ac.a_pi, &raw = ac.raw;
-    const bool hdx = mlp_headdx(), cze = act_zsaved(actC), pz = act_zsaved(actP);
+    const bool hdx = mlp_headdx(), cze = act_zsaved(actC);
     std::vector<View> pc[2], pcz[2];
     for (int n = 0; n < 2; ++n)
       mlp_critic_fwd(pg, *q[n], s, a_pi, pc[n], /*out_t*/ true, nullptr, /*last_t*/ false, hdx, &pcz[n]);
@@ -4007,6 +4024,61 @@ struct Engine {
       a.inv_b = 1.f / (float)Bv;
       pg.add(op, {raw.id, eps2.id, da.id, R_LA}, {dout.id});
     }
+    mlp_actor_backward(pg, sb, ac, dout, pdout);
+  }
+  // Offline SAC (rle_config_ext awac_lambda, AWAC): the policy phase without a gradient through the critics.  The
+  // updated critics run forward on (s, a) and on (s, a_pi) (two B-row passes each, no T images: no weight gradient
+  // reads them) down to their H -> 1 layers; OP_AWAC forms adv, w and the gradient with respect to the raw head
+  // (ops.h AwacArgs); the actor's backward from there is the online one.  No critic DX, no OP_SAC_ACTOR_BWD /
+  // EPI_SACBWD, no policy loss head.  sb.ploss: OP_AWAC's {w logp, lp, adv, w} sums of each 4-row workgroup.
+  void mlp_policy_awac(Prog& pg, StepBuild& sb, const MlpActor& ac) {
+    const int D = (int)HS.size();
+    Net* q[2] = {&net("q1"), &net("q2")};
+    Op op{};
+    op.kind = OP_AWAC;
+    AwacArgs& a = op.awac;
+    std::vector<int> rd{ac.raw.id, act_in.id, ac.logpi.id};
+    for (int n = 0; n < 2; ++n) {
+      std::vector<View> hd, hv;
+      mlp_critic_fwd(pg, *q[n], sb.s, act_in, hd, /*out_t*/ false);
+      mlp_critic_fwd(pg, *q[n], sb.s, ac.a_pi, hv, /*out_t*/ false);
+      const View qd = fwd(pg, q[n]->layers[D], {{hd[D - 1]}}, B, ACT_NONE, FwdOpt().no_t());
+      const View qv = fwd(pg, q[n]->layers[D], {{hv[D - 1]}}, B, ACT_NONE, FwdOpt().no_t());
+      a.qd[n] = qd.m;
+      a.qv[n] = qv.m;
+      rd.insert(rd.end(), {qd.id, qv.id});
+    }
+    const View dout = buf(B, 2 * A), adv = vec(B), w = vec(B);
+    op.wg_count = cdiv(Bv, 4);  // (one row per wave)
+    sb.ploss.n = op.wg_count;
+    sb.ploss.p = mem.make<float>((size_t)sb.ploss.n * 4);
+    sb.ploss.id = next_id++;
+    a.raw = ac.raw.m;
+    a.a = act_in.m;
+    a.logpi = ac.logpi.p;
+    a.dout = dout.m;
+    a.adv = adv.p;
+    a.w = w.p;
+    a.part = sb.ploss.p;
+    a.nvalid = Bv;
+    a.A = A;
+    a.mean_off = 0;
+    a.ls_off = A;
+    a.lambda = awac_lambda;
+    a.min_log_std = cfg.min_log_std;
+    a.max_log_std = cfg.max_log_std;
+    pg.add(op, rd, {dout.id, adv.id, w.id, sb.ploss.id});
+    mlp_actor_backward(pg, sb, ac, dout, PreUse{});
+  }
+  // The actor's backward + Adam from dout, the gradient with respect to its output layer's pre-activation
+  // (pdout: TD3's in-tile recomputation of dout by the first input gradient)
+  void mlp_actor_backward(Prog& pg, StepBuild& sb, const MlpActor& ac, const View& dout, const PreUse& pdout) {
+    const bool sac = algo == RLE_SAC;
+    const int D = (int)HS.size();
+    Net& pi = net("policy");
+    const Layer& Lout = pi.layers[D];
+    const View& s = sb.s;
+    const bool pz = act_zsaved(actP);
     int ngsq = 0;
     if (!sac) {
       // per-tile grad-square partials for norm/policy (rl/nn/utils.py:13-19)
@@ -4114,6 +4186,17 @@ struct Engine {
       a.target_entropy = -(float)A;
       a.logpi_part = ploss_part;
       a.nlogpi = hw;
+    } else if (offline_sac()) {  // [train/q_fn, train/policy, entropy, train/adv, train/weight]
+      // (OP_AWAC's {w logp, lp, adv, w} sums per 4 rows: the policy objective is -mean(w logp))
+      const int nw = sb.ploss.n;
+      info_sum(a, 0, sb.qloss.p, sb.qloss.n, 1, 0.5f / (float)Bv);
+      info_sum(a, 1, ploss_part, nw, 4, -1.f / (float)Bv);
+      a.kind[2] = INFO_SAC_ENT;
+      info_sum(a, 3, ploss_part + 2, nw, 4, 1.f / (float)Bv);
+      info_sum(a, 4, ploss_part + 3, nw, 4, 1.f / (float)Bv);
+      a.ninfo = 5;
+      a.logpi_part = ploss_part;
+      a.nlogpi = nw;
     } else {  // fixed temperature: [train/q_fn, train/policy, entropy]
       info_sum(a, 0, sb.qloss.p, sb.qloss.n, 1, 0.5f / (float)Bv);
       info_sum(a, 1, ploss_part, hw, 4, 1.f / (float)Bv);
@@ -4131,7 +4214,8 @@ struct Engine {
     const MlpActor ac = mlp_actor(pg);
     const MlpCritics cr = mlp_critics(pg, sb, ac);
     mlp_critic_backward(pg, sb, cr);
-    if (policy) mlp_policy(pg, sb, ac);
+    if (policy && offline_sac()) mlp_policy_awac(pg, sb, ac);
+    else if (policy) mlp_policy(pg, sb, ac);
     mlp_polyak(pg, sb);
     mlp_step_end(pg, sb);
   }
@@ -4190,7 +4274,7 @@ struct Engine {
       }
       for (size_t k = 0; k < levels[l].size(); ++k) {
         const Op& op = levels[l][k];
-        G.desc += std::string(" ") + (pg.crit_lv[l][k] ? "*" : "") + kname[op.kind];
+        G.desc += std::string(" ") + (pg.crit_lv[l][k] ? "*" : "") + (op.kind == OP_AWAC ? "awac" : kname[op.kind]);
         if (op.kind == OP_GEMM) {
           static const char* kepi[] = {"st", "adam", "mse", "qhead", "nbdot", "act", "qdot", "sacbwd", "sacfwd"};
           static_assert(sizeof(kepi) / sizeof(kepi[0]) == EPI_SACFWD + 1, "every epilogue has a name");
@@ -5270,8 +5354,13 @@ int rle_create_ext(const rle_config* cfg, const rle_config_ext* ext, rle_engine*
     // the extension as the caller compiled it: fields past ext->size read as 0
     rle_config_ext x{};
     if (ext) {
-      REQUIRE(ext->size >= (int)(offsetof(rle_config_ext, bc_alpha) + sizeof(float)),
-              "create: rle_config_ext size does not reach bc_alpha");
+      // (a size that ends inside a field would pass half of it: only the struct's field boundaries are sizes)
+      const int ends[] = {(int)(offsetof(rle_config_ext, bc_alpha) + sizeof(float)),
+                          (int)(offsetof(rle_config_ext, awac_lambda) + sizeof(float))};
+      REQUIRE(ext->size == ends[0] || ext->size == ends[1],
+              "create: rle_config_ext size " + std::to_string(ext->size) + " is not one the struct ever had; the valid "
+              "sizes, with the last field each reaches: " + std::to_string(ends[0]) + " (bc_alpha), " +
+              std::to_string(ends[1]) + " (awac_lambda)");
       std::memcpy(&x, ext, std::min<size_t>((size_t)ext->size, sizeof x));
     }
     REQUIRE(cfg->algo >= 0 && cfg->algo <= 2, "create: bad algo");
@@ -5294,12 +5383,17 @@ int rle_create_ext(const rle_config* cfg, const rle_config_ext* ext, rle_engine*
     REQUIRE(cfg->bc_lambda == 0.f || cfg->algo == RLE_TD7, "create: bc_lambda (offline mode) is TD7's");
     REQUIRE(x.bc_alpha >= 0.f && std::isfinite(x.bc_alpha), "create: bc_alpha must be a finite value >= 0");
     REQUIRE(x.bc_alpha == 0.f || cfg->algo == RLE_TD3, "create: bc_alpha (offline mode, TD3+BC) is TD3's");
+    REQUIRE(x.awac_lambda >= 0.f && std::isfinite(x.awac_lambda), "create: awac_lambda must be a finite value >= 0");
+    REQUIRE(x.awac_lambda == 0.f || cfg->algo == RLE_SAC, "create: awac_lambda (offline mode, AWAC) is SAC's");
+    REQUIRE(x.awac_lambda == 0.f || (cfg->tmp == 0.f && cfg->use_lap == 0),
+            "create: awac_lambda > 0 needs tmp == 0 (no temperature in the offline mode) and use_lap == 0");
     HIPCHK(hipSetDevice(cfg->device));
     auto h = std::make_unique<rle_engine>();
     h->e = std::make_unique<Engine>();
     Engine& e = *h->e;
     e.cfg = *cfg;
     e.bc_alpha = x.bc_alpha;
+    e.awac_lambda = x.awac_lambda;
     e.algo = cfg->algo;
     e.S = cfg->state_dim;
     e.Sp = rle::r16(e.S);

@@ -3305,6 +3305,60 @@ __device__ __forceinline__ void op_bc(const CAS BcArgs& b, int t, float* smem) {
   if (tid < A) GW(b.eye.t)[tidx(b.eye.rbs, tid, tid)] = q_abs;
 }
 
+// ---------------------------------------------------------------- advantage-weighted policy step (offline SAC)
+// (ops.h AwacArgs; the extended instance alone.  One row per wave, 4 per workgroup, as the loss heads: lane l
+// holds columns l and l + 64 of its row, so a row's loads are one round trip and its sums over A one wave_sum)
+__device__ __forceinline__ void op_awac(const CAS AwacArgs& s, int t, float* smem) {
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int b = t * 4 + wave;  // wave-uniform
+  const float c = (float)0.9189385332046727;  // 0.5 log(2 pi)
+  const float amax = 1.f - 1e-6f;
+  float wlp = 0.f, lpi = 0.f, adv = 0.f, w = 0.f;
+  if (b < s.nvalid) {
+    adv = fminf(mat_ld(s.qd[0], b, 0), mat_ld(s.qd[1], b, 0)) - fminf(mat_ld(s.qv[0], b, 0), mat_ld(s.qv[1], b, 0));
+    w = fminf(expf(__fdiv_rn(adv, s.lambda)), 100.f);
+    const float wb = w / (float)s.nvalid;
+    float lp = 0.f, corr = 0.f;
+#pragma unroll 1
+    for (int j = lane; j < s.A; j += 64) {
+      const float mu = mat_ld(s.raw, b, s.mean_off + j);
+      const float lsr = mat_ld(s.raw, b, s.ls_off + j);
+      const float ls = fminf(fmaxf(lsr, s.min_log_std), s.max_log_std);
+      const float sd = expf(ls);
+      const float var = sd * sd;
+      const float ac = fminf(fmaxf(mat_ld(s.a, b, j), -amax), amax);
+      const float d = atanhf(ac) - mu;
+      lp += -(d * d) / (2.f * var) - ls - c;
+      corr += logf((1.f - ac * ac) + 1e-6f);
+      const float gmu = -wb * d / var;
+      float gls = -wb * ((d * d) / var - 1.f);
+      if (!(lsr >= s.min_log_std && lsr <= s.max_log_std)) gls = 0.f;
+      mat_st(s.dout, b, s.mean_off + j, gmu);
+      mat_st(s.dout, b, s.ls_off + j, gls);
+    }
+    lp = wave_sum(lp);  // (every lane of the wave is here: lanes without a column add 0)
+    corr = wave_sum(corr);
+    wlp = w * (lp - corr);
+    lpi = G(s.logpi)[b];
+    if (lane == 0) {
+      GW(s.adv)[b] = adv;
+      GW(s.w)[b] = w;
+    }
+  }
+  // the workgroup's four rows, in row order (rows past nvalid: zeros)
+  if (lane == 0) {
+    smem[wave * 4 + 0] = wlp;
+    smem[wave * 4 + 1] = lpi;
+    smem[wave * 4 + 2] = adv;
+    smem[wave * 4 + 3] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const int k = threadIdx.x;
+    GW(s.part)[(size_t)t * 4 + k] = (smem[k] + smem[4 + k]) + (smem[8 + k] + smem[12 + k]);
+  }
+}
+
 // ---------------------------------------------------------------- dispatch
 
 // TRACE: compiled with the phase stamps (RLE_TRACE=1 runs); the production instance has
@@ -3407,7 +3461,9 @@ __global__ __launch_bounds__(kThreads, RLE_WAVES) void rle_level(unsigned e0, un
     RLE_OP(OP_NOISE, op_noise(op.sample, t))
     RLE_OP(OP_FOLDBIAS, op_foldbias(op.fb))
     // (kinds past 15, ops.h OpKind: low bits 0, kind >> 4 in the variant field; the TD7 family's instances)
-    RLE_OP(0, if (ks_family(KS) != KS_MLP && vid == (OP_BC >> 4)) op_bc<ks_family(KS) == KS_EXT>(op.bc, t, smem))
+    // (OP_AWAC, offline SAC: the extended instance's alone)
+    RLE_OP(0, if (ks_family(KS) != KS_MLP && vid == (OP_BC >> 4)) op_bc<ks_family(KS) == KS_EXT>(op.bc, t, smem);
+           else if (ks_family(KS) == KS_EXT && vid == (OP_AWAC >> 4)) op_awac(op.awac, t, smem))
 #undef RLE_OP
     default: break;
   }

@@ -34,6 +34,7 @@ enum OpKind : int {
   // Kinds past 15: a level-launch entry keeps a kind's low four bits in bits 16-19 (0 for these) and, for a
   // non-GEMM op, kind >> 4 in the variant field (LevelArgs::entry), so every earlier entry is unchanged.
   OP_BC = 16,           // TD7 offline: the behaviour-cloning term's scalars and action-gradient operand (BcArgs)
+  OP_AWAC = 32,         // offline SAC: the advantage-weighted policy step's row-wise op (AwacArgs; the extended instance)
 };
 
 // ---------------------------------------------------------------- tensor images
@@ -592,6 +593,32 @@ struct BcArgs {
   float* out;            // mode 1: [1]
 };
 
+// Offline SAC policy step (rle_config_ext awac_lambda > 0, AWAC): the advantage-weighted log-likelihood of the
+// batch's stored action under the squashed Gaussian of the raw head, row by row (one row per wave, 4 rows per
+// workgroup, as the loss heads; lane l holds columns l and l + 64, and the sums over the A columns are one
+// wave_sum, so no reduction over A leaves the wave):
+//   l = clamp(ls, min, max), sigma = exp(l);  adv = min(qd0, qd1) - min(qv0, qv1);  w = min(exp(adv / lambda), 100)
+//   a_c = clamp(a, -(1 - 1e-6), 1 - 1e-6) (fp32 constants), u = atanh(a_c)
+//   logp = sum_j [-(u - mu)^2 / (2 sigma^2) - l - 0.5 log(2 pi)] - sum_j log(1 - a_c^2 + 1e-6)
+//   dout(mean) = -(w / nvalid) (u - mu) / sigma^2
+//   dout(ls)   = -(w / nvalid) ((u - mu)^2 / sigma^2 - 1) where min <= ls <= max, else 0
+// over rows < nvalid and columns < A: rows past nvalid store nothing (dout's padded rows and columns stay zero)
+// and add exactly zero to the partials.  part[wg][4] = the sums over the workgroup's 4 rows of {w logp, log pi of
+// the policy's own rsample (logpi, for the `entropy` info), adv, w}, added as (r0 + r1) + (r2 + r3); the step end
+// adds the workgroups' partials as it adds the loss heads' -- an order fixed by nvalid alone.  No gradient reaches
+// the critics: qd / qv are forward-only passes.
+struct AwacArgs {
+  Mat raw;               // raw head output [2B][2A(p)]: mean | log_std (rows < nvalid: the policy rows)
+  Mat a;                 // the batch's action [B][Ap]
+  Mat qd[2], qv[2];      // q1, q2 on (s, a) and on (s, a_pi): [B][1]
+  const float* logpi;    // [2B] log pi of the rsample (policy rows first)
+  Mat dout;              // grad wrt the raw output [B][2A(p)] (N + T)
+  float* adv; float* w;  // [B] out
+  float* part;           // [ceil(nvalid / 4)][4] out
+  int nvalid, A, mean_off, ls_off;
+  float lambda, min_log_std, max_log_std;
+};
+
 struct FlatArgs {   // POLYAK / COPY / MAXRED
   float* dst; const float* src; long long n;
   float tau, omt; int self_alias;     // self_alias: p <- tau*p + p*(1-tau) (TD3 quirk Q2)
@@ -625,6 +652,7 @@ struct Op {
     CtrlArgs ctrl;
     FoldBiasArgs fb;
     BcArgs bc;
+    AwacArgs awac;
   };
 };
 // kernels.hip gemm_v touches the descriptor's 64-byte lines by fixed offsets from &gemm (its
@@ -632,7 +660,7 @@ struct Op {
 static_assert(sizeof(HeadArgs) <= sizeof(PreArgs), "GemmArgs: the fused head shares the pre-GEMM's fields");
 static_assert(sizeof(Op) % 64 == 0 && offsetof(Op, gemm) == 16, "Op layout (descriptor line touches)");
 static_assert(16 + sizeof(HeadArgs) <= 8 * 64 && 16 + sizeof(StepEndArgs) <= 8 * 64 && 16 + sizeof(SampleArgs) <= 8 * 64 &&
-                  16 + sizeof(BcArgs) <= 8 * 64,
+                  16 + sizeof(BcArgs) <= 8 * 64 && 16 + sizeof(AwacArgs) <= 8 * 64,
               "rle_level touches 8 descriptor lines of a non-GEMM op");
 static_assert(offsetof(GemmArgs, A) == 0xb0 && offsetof(GemmArgs, B) == 0x1a0 && offsetof(GemmArgs, out) == 0x290 &&
                   offsetof(GemmArgs, noise) == 0x2f0 && offsetof(GemmArgs, nbx) == 0x370 &&

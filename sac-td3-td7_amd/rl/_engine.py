@@ -52,12 +52,14 @@ class ConfigExt(ctypes.Structure):
     """Mirror of ``rle_config_ext`` (include/rle.h): settings added after ``rle_config`` was frozen.
     ``size`` is what this mirror knows of the struct; the library reads every field past it as 0."""
 
-    _fields_ = [("size", _int), ("bc_alpha", ctypes.c_float)]
+    _fields_ = [("size", _int), ("bc_alpha", ctypes.c_float), ("awac_lambda", ctypes.c_float)]
 
 
-def make_config_ext(bc_alpha=0.0) -> ConfigExt:
-    """``bc_alpha`` (TD3): 0 online; > 0 the offline (TD3+BC) policy step's alpha (rle_config_ext bc_alpha)."""
-    return ConfigExt(ctypes.sizeof(ConfigExt), float(bc_alpha))
+def make_config_ext(bc_alpha=0.0, awac_lambda=0.0) -> ConfigExt:
+    """``bc_alpha`` (TD3): 0 online; > 0 the offline (TD3+BC) policy step's alpha (rle_config_ext bc_alpha).
+    ``awac_lambda`` (SAC at a fixed temperature of 0): 0 online; > 0 the offline (AWAC) policy step's lambda
+    (rle_config_ext awac_lambda)."""
+    return ConfigExt(ctypes.sizeof(ConfigExt), float(bc_alpha), float(awac_lambda))
 
 
 # rle_config act_* codes (include/rle.h RLE_ACT_*): 0 = the reference default of that net

@@ -13,17 +13,37 @@ class SAC(EngineAgent):
 
     Constructor arguments as the reference (sac.py:27-42) plus ``hidden``,
     ``batch_size``, ``seed`` and ``device``.  ``max_grad_norm`` is stored but, as in
-    the reference, never applied."""
+    the reference, never applied.
+
+    ``offline=True`` trains from a fixed dataset with AWAC (Nair et al. 2020): the critic step is SAC's at a fixed
+    temperature of 0, and the policy step maximises the advantage-weighted log-likelihood of the batch's stored
+    action, ``L = -mean(w * log pi(a | s))`` with ``w = min(exp((Q(s, a) - Q(s, a_pi)) / lmbda), 100)`` detached
+    (``Q = min(q1, q2)`` of the updated critics, ``a_pi`` the policy's own rsample).  No gradient passes through
+    the critics.  The info dict is ``train/q_fn``, ``train/policy``, ``entropy``, ``train/adv`` (mean advantage)
+    and ``train/weight`` (mean w).  ``offline`` forces ``tmp = 0``; ``offline=False`` ignores ``lmbda``."""
 
     ALG = "sac"
     ALGO = E.RLE_SAC
     OPTIM_NETS = ("policy", "q1", "q2")
+    offline = False  # (class defaults: an agent pickled before the offline mode existed loads as online)
+    lmbda = 1.0
 
     def __init__(self, env_id: str, discount_factor: float = 0.99, policy_lr: float = 3e-4,
                  critic_lr: float = 3e-4, min_log_std: float = -20.0, max_log_std: float = 2.0,
                  tau: float = 0.005, tmp: float = -1.0, use_lap: bool = False,
                  max_grad_norm: float = float("inf"), make_nn=None, *, hidden: int = 256,
-                 batch_size: int = 256, seed: int | None = None, device=None, **make_nn_kwargs) -> None:
+                 batch_size: int = 256, seed: int | None = None, device=None, offline: bool = False,
+                 lmbda: float = 1.0, **make_nn_kwargs) -> None:
+        self.offline = bool(offline)
+        self.lmbda = float(lmbda)
+        if self.offline:
+            if tmp not in (-1.0, 0.0):
+                raise ValueError("SAC(offline=True) runs at a fixed temperature of 0: leave tmp at its default or pass 0")
+            if not (self.lmbda > 0.0 and np.isfinite(self.lmbda)):
+                raise ValueError("SAC(offline=True): lmbda must be a finite value > 0")
+            tmp = 0.0
+            # (_ext: every engine this agent builds -- _rebuild, pickle, deepcopy, to() -- carries it)
+            self._ext = dict(awac_lambda=self.lmbda)
         self.auto_tmp_mode = tmp < 0.0
         self.discount_factor = discount_factor
         self.min_log_std, self.max_log_std = min_log_std, max_log_std
@@ -49,6 +69,8 @@ class SAC(EngineAgent):
         return super().train_n(replay_buffer, batch_size, n_ops)
 
     def _info_keys(self):
+        if getattr(self, "_ext", {}).get("awac_lambda", 0.0) > 0:  # (the engine's offline programs)
+            return ("train/q_fn", "train/policy", "entropy", "train/adv", "train/weight")
         if self.auto_tmp_mode:  # sac.py:268-290
             return ("train/q_fn", "tmp", "norm/tmp", "train/policy", "train/tmp", "entropy")
         return ("train/q_fn", "train/policy", "entropy")

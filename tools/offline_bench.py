@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""What the offline modes cost (DESIGN.md "Offline TD7", "Offline TD3"): writes profiles/offline_bench.json
-(--algo td7, the default) or profiles/offline_td3_bench.json (--algo td3).
+"""What the offline modes cost (DESIGN.md "Offline TD7", "Offline TD3", "Offline SAC"): writes
+profiles/offline_bench.json (--algo td7, the default), profiles/offline_td3_bench.json (--algo td3) or
+profiles/offline_sac_bench.json (--algo sac).
 
 The flagship shape of bench.py -- TD7 on Humanoid-v4, hidden 256, batch 256, a 1M-row LAP replay -- as two
 engines in one process on one replay each, one online (rle_config bc_lambda 0) and one offline (bc_lambda
@@ -13,8 +14,12 @@ is measured against), the levels per policy / plain step of both, and the offlin
 --algo td3: the same for TD3+BC on bench.py's TD3 shape -- HalfCheetah-v4, hidden 256, batch 256, a 1M-row
 replay -- online (rle_create) against offline (rle_config_ext bc_alpha, --alpha, default 2.5).
 
-usage: python tools/offline_bench.py [--algo td7|td3] [--steps 2000] [--rounds 5] [--warmup 200] [--lmbda 0.1]
-                                     [--alpha 2.5] [--out FILE]
+--algo sac: the same for AWAC on bench.py's SAC shape -- Humanoid-v4, hidden 256, batch 256, a 1M-row replay --
+online at a fixed temperature of 0 (rle_create, tmp 0) against offline (rle_config_ext awac_lambda, --awac,
+default 1.0).
+
+usage: python tools/offline_bench.py [--algo td7|td3|sac] [--steps 2000] [--rounds 5] [--warmup 200] [--lmbda 0.1]
+                                     [--alpha 2.5] [--awac 1.0] [--out FILE]
 """
 
 from __future__ import annotations
@@ -39,13 +44,15 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--lmbda", type=float, default=0.1)
-    ap.add_argument("--algo", choices=("td7", "td3"), default="td7")
+    ap.add_argument("--algo", choices=("td7", "td3", "sac"), default="td7")
     ap.add_argument("--alpha", type=float, default=2.5)
+    ap.add_argument("--awac", type=float, default=1.0)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    td3 = args.algo == "td3"
+    td3, sac = args.algo == "td3", args.algo == "sac"
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", "offline_td3_bench.json" if td3 else "offline_bench.json")
+        name = "offline_td3_bench.json" if td3 else "offline_sac_bench.json" if sac else "offline_bench.json"
+        args.out = os.path.join(REPO, "profiles", name)
 
     import torch
     from rl import _engine as E
@@ -58,22 +65,27 @@ def main():
         if td3:  # (bench.py's TD3 run: no LAP; online through rle_create, offline through rle_create_ext)
             cfg = E.make_config(E.RLE_TD3, s_dim, a_dim, H, B, use_lap=False, seed=111)
             eng = E.Engine(cfg, ext=E.make_config_ext(bc_alpha=weight) if weight else None)
+        elif sac:  # (online: the fixed-temperature program at tmp = 0, whose critic step the offline mode keeps)
+            cfg = E.make_config(E.RLE_SAC, s_dim, a_dim, H, B, use_lap=False, seed=111, tmp=0.0)
+            eng = E.Engine(cfg, ext=E.make_config_ext(awac_lambda=weight) if weight else None)
         else:
             eng = E.Engine(E.make_config(E.RLE_TD7, s_dim, a_dim, H, B, use_lap=True, seed=111, bc_lambda=weight))
         for net, params in nets.items():
             for name, v in params.items():
                 eng.set_param(net, name, v)
-        rep = E.Replay(N_REPLAY, s_dim, a_dim, not td3, device=0)
+        rep = E.Replay(N_REPLAY, s_dim, a_dim, not (td3 or sac), device=0)
         rep.fill_random(N_REPLAY, seed=seed)
         eng.bind(rep)
         return eng, rep
 
-    engs = {"online": engine(0.0, 0), "offline": engine(args.alpha if td3 else args.lmbda, 0)}
+    engs = {"online": engine(0.0, 0), "offline": engine(args.alpha if td3 else args.awac if sac else args.lmbda, 0)}
     what = (f"TD3 HalfCheetah-v4 hidden {H} batch {B} {N_REPLAY} rows" if td3
+            else f"SAC Humanoid-v4 tmp 0 hidden {H} batch {B} {N_REPLAY} rows" if sac
             else f"TD7 Humanoid-v4 hidden {H} batch {B} LAP {N_REPLAY} rows")
     res = {"device": torch.cuda.get_device_name(0),
            "config": f"{what}, rle_step_timed({args.steps}) x {args.rounds} per mode, alternating; offline "
-                     + (f"bc_alpha {args.alpha}" if td3 else f"bc_lambda {args.lmbda}"),
+                     + (f"bc_alpha {args.alpha}" if td3 else f"awac_lambda {args.awac}" if sac
+                        else f"bc_lambda {args.lmbda}"),
            "levels_per_step": {}, "bursts_steps_per_s": {k: [] for k in engs}}
     for k, (eng, _) in engs.items():
         lp, lpl = eng.graph_stats()
