@@ -2635,16 +2635,20 @@ struct PendTab {
 };
 __device__ __forceinline__ PendTab pend_prepare(const CAS SampleArgs& s, float* smem) {
   const int tid = threadIdx.x, n = s.pend_n;
+  // the tables are laid out for the batch padded to 16 rows (engine.cpp prio_sample_fused sizes them so): pend_n is
+  // the batch's valid rows, any 1..1024, and 12 n / 20 n bytes of an odd n would leave the fp64 tables -- and the
+  // LDS atomics on them -- 4 bytes off their alignment
+  const int np = (n + 15) & ~15;
   int ns = 64;
-  while (ns < 2 * n) ns <<= 1;  // hash slots: load factor <= 1/2
-  const int r0 = max(8 * ns, 20 * n);
+  while (ns < 2 * np) ns <<= 1;  // hash slots: load factor <= 1/2
+  const int r0 = max(8 * ns, 20 * np);
   char* L = (char*)smem;
   int* keys = (int*)L;
   int* last = keys + ns;
   int* wkey = (int*)L;  // (records: after the hash is dead)
-  int* wnext = wkey + n;
-  float* wnew = (float*)(wnext + n);
-  double* wdel = (double*)(L + 12 * n);  // (12 n: 8-aligned, n a multiple of 16)
+  int* wnext = wkey + np;
+  float* wnew = (float*)(wnext + np);
+  double* wdel = (double*)(L + 12 * np);  // (12 np: 8-aligned, np a multiple of 16)
   const int nbc = (int)((s.cap + kBlk - 1) / kBlk);
   double* bdel = (double*)(L + r0);
   int* bhead = (int*)(bdel + nbc);

@@ -41,7 +41,9 @@ def _case(alg, S, A, H, B, seed, hidden_sizes=None, zs_dim=None, use_lap=None, b
 # criteria of tests/test_shape_edges.py (float32 oracle against float64) at that seed and took the first of
 # seed + 100 k that meets them: td7-h272 (204: one of 74k zs3 weights 1.9e-5 from float64 after 7 steps),
 # td7-h512 (2805: at this width 5-20 of 3.2M elements land past 1e-5 for most seeds) and sac-min (217: with
-# one row, log(1 - a^2 + 1e-6) of a saturated action is 2.5e-5 off in float32).
+# one row, log(1 - a^2 + 1e-6) of a saturated action is 2.5e-5 off in float32).  The three cases for the 64-row
+# tiles (td7-w50, sac-w50, td3-w100: 122 - 124) met the host criteria at their first seed (worst step-1 moment
+# distance 7.4e-7 / 8.1e-7 / 3.2e-7), and no (case, plan) pair of tests/plan_cases.py needed a reseed.
 CASES = {
     "td7-b1": _case("td7", 11, 3, 32, 1, 101, note="one valid row, 15 masked"),
     "td7-min": _case("td7", 1, 1, 4, 17, 102, zs_dim=4, note="every dimension at its minimum; K = 1; 2 row blocks"),
@@ -64,6 +66,10 @@ CASES = {
     "sac-a25": _case("sac", 11, 25, 32, 17, 119, note="2A = 50: the standalone rsample"),
     "sac-h260": _case("sac", 16, 24, 260, 15, 120, hidden_sizes=[260, 260], note="R just past 256, % 16 != 0"),
     "sac-max_in": _case("sac", 1024, 128, 32, 16, 121, note="largest inputs"),
+    # 64-row tiles (rle_plan wide, tests/plan_cases.py): a batch that pads to one 64-row block / to 112 rows
+    "td7-w50": _case("td7", 11, 3, 64, 50, 122, note="pads to one 64-row block, 14 masked rows"),
+    "sac-w50": _case("sac", 11, 3, 64, 50, 123, note="pads to one 64-row block, 14 masked rows"),
+    "td3-w100": _case("td3", 11, 3, 64, 100, 124, note="pads to 112 rows: no whole 64-row blocks, wide_tiles declines"),
 }
 
 INFO_KEYS = {"td7": ("train/encoder", "train/q_fn", "train/policy"),

@@ -65,6 +65,11 @@ def test_table_covers_the_edges_it_names():
     assert all(x.S == 1 and x.A == 1 and x.H == 4 for k, x in c.items() if k.endswith("-min"))
     assert len(c["td3-deep6"].hidden_sizes) == 6
     assert len({x.seed for x in c.values()}) == len(c)
+    # wide_tiles: every row piece whole 64-row blocks (B pads to 16 rows first)
+    r16 = lambda b: -(-b // 16) * 16  # noqa: E731
+    assert r16(c["td7-w50"].B) == 64 == r16(c["sac-w50"].B) and c["td7-w50"].B == 50 == c["sac-w50"].B
+    assert r16(c["td3-w100"].B) == 112 and r16(c["td3-w100"].B) % 64
+    assert c["td7-w50"].H == c["sac-w50"].H == c["td3-w100"].H == 64                        # N % wide == 0 for 32, 64
 
 
 def _create(cfg):

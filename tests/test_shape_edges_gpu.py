@@ -27,9 +27,10 @@ from test_engine_gpu import assert_params_close  # noqa: E402
 from test_offline_gpu import offline_engine  # noqa: E402
 
 
-def _engine(case, plan=None):
+def _engine(case, plan=None, g=None):
+    """(g: a golden other than the table's, e.g. another target_update_rate -- no oracle run then)"""
     c = CASES[case]
-    g = reference(case)["g"]
+    g = reference(case)["g"] if g is None else g
     with edge_env(case):
         if c.bc_lambda:
             return offline_engine(g, c.bc_lambda, plan)
@@ -58,15 +59,14 @@ def _check_lap_and_bounds(case, eng, rep, run, t):
         np.testing.assert_allclose(eng.value_bounds(), run["vb"][t].astype(np.float32), rtol=1e-4, atol=1e-4)
 
 
-@pytest.mark.parametrize("case", list(CASES))
-def test_edge_case_trains_like_the_oracle(case):
-    """Step 1 alone (single-step program), then the remaining steps as one burst (the multi-step and
-    remainder programs at this shape)."""
+def check_trains_like_the_oracle(case, plan=None):
+    """The criteria of test_edge_case_trains_like_the_oracle for ``case`` under ``plan`` (None: the default plan;
+    tests/test_plan_edges_gpu.py calls it per (case, plan) pair).  Returns the worst distances it printed."""
     c = CASES[case]
     ref = reference(case)
     f32, f64 = ref["f32"], ref["f64"]
     n = c.n_steps
-    eng, rep = _engine(case)
+    eng, rep = _engine(case, plan)
     tp = _tapes(case)
     eng.set_tapes(u=tp["u"], eps=tp["eps"], eps_pi=tp.get("eps_pi"))
     infos = [eng.step(1)[0]]
@@ -102,6 +102,17 @@ def test_edge_case_trains_like_the_oracle(case):
         assert_params_close(eng.get_param(net, name, v.shape), v, tol, (net, name), bulk=0.99)
     if c.alg == "sac":
         np.testing.assert_allclose(eng.get_param("tmp", "log_alpha"), f32["log_alpha"].reshape(-1), rtol=1e-5, atol=1e-7)
+    return {"gradient": worst, "bulk": bulk, "far": far}
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_edge_case_trains_like_the_oracle(case):
+    """Step 1 alone (single-step program), then the remaining steps as one burst.  TD3 / SAC: the burst replays
+    the multi-step and remainder programs at this shape.  TD7: every case hard-updates every 3 steps, so each
+    window of its 6-step program holds a hard update and the burst replays single-step programs around the
+    hard updates only; TD7's multi-step programs run at edge shapes in tests/test_plan_edges_gpu.py
+    (test_multistep_program_equals_single_steps, target_update_rate 250)."""
+    check_trains_like_the_oracle(case)
 
 
 @pytest.mark.parametrize("case", list(CASES))
