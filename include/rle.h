@@ -433,6 +433,31 @@ int rle_aql_selftest(void);
  * *op_bytes: the size of one op descriptor.  A dispatch over the workgroup bound: RLE_EHIP and *n = 0. */
 int rle_level_plan(const int* kind, const int* vid, const int* wg_begin, int nops, int nwg, unsigned long long d_ops,
                    unsigned long long next_ops, int next_nops, int ks, unsigned* out, int cap, int* n, int* op_bytes);
+/* The level scheduler alone (no GPU, no HIP or HSA call, diagnostic switches off) on a made-up program of nitems
+ * items holding nops ops, in program order.  Op q belongs to item item[q] (item[0] = 0; item[q] is item[q-1] or
+ * item[q-1] + 1, so the ops of an item are consecutive and every item has at least one), is of kind kind[q]
+ * (ops.h OpKind: GEMM 1, sampler gather 4, loss head 5, step end 9, ...), takes wg_count[q] workgroups, and
+ * carries attr[4q .. 4q+3], the only other fields the scheduler's weights read: for a GEMM {R, tn, epi,
+ * has_pre} (weight R * tn / 1024, + adam_w when epi is 1, the Adam epilogue, + pl_w when has_pre >= 3); for
+ * the sampler gather {lap, 0, 0, 0} (lap_w, or uni_w when 0); for the step end {mode, 0, 0, 0} (tiny_w, or 8
+ * when tiny_w is 0, unless mode is 1); ignored for every other kind (the loss head weighs head_w, the rest 8).
+ * Item i reads resources rd[rd_off[i] .. rd_off[i+1] - 1] and writes wr[wr_off[i] .. wr_off[i+1] - 1]
+ * (rd_off, wr_off: nitems + 1 non-decreasing offsets from 0; a negative resource id orders nothing).
+ * Of *plan only balance, tiny_w, uni_w, tiny_wg, pl_w, lap_w, head_w, adam_w and lpt are read, as resolved
+ * values (-1 is an error here, not "default").  wg_cap > 0: workgroups a level may hold before a further
+ * item is deferred (1 << 30: none).  Out, per op q: level[q], its dependency level; pos[q], its place in that
+ * level's launch order; wg_begin[q], the level's workgroups before it. */
+int rle_schedule_plan(const int* item, const int* kind, const int* wg_count, const int* attr, int nops, const int* rd_off,
+                      const int* rd, const int* wr_off, const int* wr, int nitems, const rle_plan* plan, int wg_cap,
+                      int* level, int* pos, int* wg_begin);
+/* The conflict sweep of the RLE_HAZARD=1 level check alone (no GPU): n byte ranges [lo[k], hi[k]) (lo < hi), in
+ * any order, that op op[k] (0 <= op[k] < nops) reads or, write[k] != 0, stores; item[j]: the program item of op
+ * j.  Two ranges conflict when they share a byte, at least one of them is stored, and they belong to different
+ * ops of different items.  Returns 0 and *op_a = *op_b = -1 when none do; else 1 with the first conflict met
+ * when the ranges are swept by ascending lo: *op_b the op of the range the sweep stands at, *op_a that of the
+ * range begun before it that still covers its first byte.  Negative: an RLE_* error. */
+int rle_hazard_scan(const unsigned long long* lo, const unsigned long long* hi, const int* write, const int* op, int n,
+                    const int* item, int nops, int* op_a, int* op_b);
 /* Copy all weights/optimizer state/counters of src into dst (checkpoint agent,
  * ckpt_agent.load_state_dict(agent), run_w_checkpoint.py:140), and the act path's exploration counter
  * (rle_get_act_counter).  Same algorithm and identical layer shapes required; the batch size may differ. */

@@ -212,6 +212,10 @@ SIGNATURES = {
     "rle_level_plan": (_int, [ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int), _int, _int,
                               ctypes.c_ulonglong, ctypes.c_ulonglong, _int, _int, ctypes.POINTER(ctypes.c_uint), _int,
                               ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "rle_schedule_plan": (_int, [ctypes.POINTER(_int)] * 4 + [_int] + [ctypes.POINTER(_int)] * 4 + [_int, _vp, _int]
+                          + [ctypes.POINTER(_int)] * 3),
+    "rle_hazard_scan": (_int, [ctypes.POINTER(ctypes.c_ulonglong)] * 2 + [ctypes.POINTER(_int)] * 2 + [_int,
+                        ctypes.POINTER(_int), _int, ctypes.POINTER(_int), ctypes.POINTER(_int)]),
     "rle_eval": (_int, [_vp, _int, _cs, _cs, _f32p, _f32p, _int, _f32p]),
     "rle_sac_rsample": (_int, [_vp, _f32p, _f32p, _f32p, _int, _f32p, _f32p]),
     "rle_get_info": (_int, [_vp, _int, _f32p]),

@@ -143,7 +143,7 @@ def test_td7_head_variants_match_reference(name, variant):
                                   "sac_humanoid", "td7_tiny_act", "td7_tiny_act_id", "td3_tiny_act", "sac_tiny_act"])
 def test_level_hazards(name, monkeypatch):
     """RLE_HAZARD=1: no byte that one op of a level stores is read or stored by another op of the
-    same level (engine.cpp level_hazards: each op's accesses replayed from its descriptor) in any
+    same level (plan.cpp level_hazards: each op's accesses replayed from its descriptor) in any
     program the engine builds -- single-step, multi-step, hard-update and eval graphs; then one
     step runs."""
     monkeypatch.setenv("RLE_HAZARD", "1")
@@ -156,7 +156,7 @@ def test_level_hazards(name, monkeypatch):
                                   "td7_tiny_act", "td7_tiny_act_id", "td3_tiny_act", "sac_tiny_act"])
 def test_gemm_address_audit(name, monkeypatch):
     """RLE_AUDIT=1: every byte range each GEMM op's workgroups can load or store (the kernel's
-    address arithmetic replayed on the host, engine.cpp audit_gemm) lies inside one live device
+    address arithmetic replayed on the host, plan.cpp audit_gemm) lies inside one live device
     allocation, for every program the engine builds; then one step runs."""
     monkeypatch.setenv("RLE_AUDIT", "1")
     g = load_golden(name)

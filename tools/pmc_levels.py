@@ -108,7 +108,7 @@ if MODEL:
     print("sum " + " ".join(f"{mt[kk]:7.0f}" for kk in ("act_r", "act_w", "w_r", "adam", "other")) +
           f" {tm:8.0f} {mt['pmc']:8.0f} {mt['pmc'] / max(tm, 1):5.2f}")
     if all(m.get("xcd_r") is not None for m in MODEL.values()):
-        # per-XCD model: every XCD's L2 fetches its own copy of what its workgroups read (engine.cpp LevelTraffic)
+        # per-XCD model: every XCD's L2 fetches its own copy of what its workgroups read (plan.h LevelTraffic)
         # + the unique bytes stored (activations, Adam's stores) + the sampler / priority / reductions' bytes
         print("\nper-XCD read model against the counters, KB: reads (2 x FETCH_SIZE) and stores (WRITE_SIZE) apart")
         print(f"{'lvl':>3} {'xcd_r':>8} {'2xFETCH':>8} {'x':>5} {'stores':>8} {'WRITE':>8} {'x':>5} {'model':>8} {'pmc':>8} {'cover':>6}")
