@@ -270,6 +270,20 @@ int rle_destroy(rle_engine* e);
 int rle_plan_default(rle_plan* out);
 int rle_set_plan(rle_engine* e, const rle_plan* plan);
 int rle_get_plan(rle_engine* e, rle_plan* out);
+/* Gradient-norm clipping in the device step (torch.nn.utils.clip_grad_norm_ per optimizer, error_if_nonfinite
+ * False: a NaN or inf norm propagates).  One max_norm for every optimizer of a gradient step: TD7's encoder, the
+ * critics (q1 + q2, one optimizer) and SAC's policy every step, the TD7 / TD3 policy on policy steps; SAC's
+ * temperature is never clipped.  total = sqrt(sum over the optimizer's tensors of sum g^2),
+ * coef = min(1, max_norm / (total + 1e-6)), g <- g * coef.  TD3's norm/policy info stays the norm before clipping.
+ * 0 or +inf: off (the default): the unclipped step programs op for op, on the kernel instance they run on today.
+ * > 0: clip every optimizer of the step to this global L2 norm (the programs then run on a kernel instance of
+ * their own, without RLE_FUSE_NBDEFER).  Before the engine's first step only (RLE_ESTATE after it); negative or
+ * NaN: RLE_EINVAL.  rle_copy_state, rle_copy_nets and rle_state_* work between engines whose setting differs. */
+int rle_set_grad_clip(rle_engine* e, float max_norm);
+int rle_get_grad_clip(rle_engine* e, float* max_norm);  /* (0: off) */
+/* {total, coef} of the last update of each optimizer: [0] critics, [1] policy, [2] TD7 encoder (NaN for an
+ * optimizer that has not stepped or when clipping is off).  Syncs. */
+int rle_grad_clip_stats(rle_engine* e, float* out6);
 /* Bind the replay the step samples from (the replay_buffer arg of train_ops). */
 int rle_bind_replay(rle_engine* e, rle_replay* r);
 /* Parameter import/export in the reference's state_dict layout (Agent.load_state_dict,

@@ -23,6 +23,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -322,6 +323,9 @@ struct Engine {
   // the rle_level instance this engine's programs run on (ops.h KernelSet): the agent's own set, or the
   // extended instance when the plan asks for its opt-in paths
   int kernel_set() const {
+    // (gradient clipping: EPI_GSQ, the scaled Adam pass over normed operands and OP_CLIP are KS_CLIP's alone; it
+    // holds KS_ACT's code, so every activation and offline mode clips)
+    if (clip_on()) return KS_CLIP;
     // (LeakyReLU / SiLU / GELU: the ELU variants' second dispatch is KS_ACT's alone, ops.h act_vslot)
     if (std::max({actP, actC, actE}) > ACT_TANH) return KS_ACT;
     if (!acts_default) return KS_EXT;  // (the activation variants outside the agent's own set)
@@ -333,6 +337,12 @@ struct Engine {
     if (plan.rb || (plan.fuse_on & RLE_FUSE_PRIOSAMPLE) || plan.wide) return KS_EXT;
     return algo == RLE_TD7 ? KS_TD7 : KS_MLP;
   }
+  // Gradient clipping (rle_set_grad_clip): 0 = off.  clip_buf: per optimizer (0 critics, 1 policy, 2 TD7 encoder)
+  // {total, coef, the Adam passes' scalar, -}, written by OP_CLIP; clip_id: their scheduler resources.
+  float clip_max = 0.f;
+  float* clip_buf = nullptr;
+  int clip_id[3] = {-1, -1, -1};
+  bool clip_on() const { return clip_max > 0.f; }
   void resolve_plan() {
     if (plan.steps_per_graph < 0) plan.steps_per_graph = algo == RLE_TD3 ? 16 : algo == RLE_SAC ? 8 : 6;
     // (SAC's target critics' raw-head pre-GEMM consumers: 32 measured +1.0% over 64, 2 pairs)
@@ -1041,6 +1051,8 @@ struct Engine {
   static constexpr unsigned kActFusions = RLE_FUSE_PRELAYER | RLE_FUSE_PRE | RLE_FUSE_TWOSTAGE | RLE_FUSE_SACPRE;
   static constexpr unsigned kCriticActFusions = RLE_FUSE_QDOT | RLE_FUSE_HEADDX;
   bool fused(unsigned bit) const {
+    // (clipped programs: the AvgL1Norm backward stays an op of its own, so kDwNb needs no norm-pass and no scaled form)
+    if (clip_on() && (bit & RLE_FUSE_NBDEFER)) return false;
     if (!acts_default && (bit & kActFusions)) return false;
     if (!acts_default && actC == ACT_NONE && (bit & kCriticActFusions)) return false;
     return (bit & RLE_FUSE_OPT_IN) ? (plan.fuse_on & bit) != 0 : !(plan.fuse_off & bit);
@@ -1206,6 +1218,47 @@ struct Engine {
     DxOpt& no_t() { return t = false, *this; }
     DxOpt& pl_source(bool on) { return pl_src = on, *this; }
   };
+  // One clipped optimizer update of a step: the per-tile partials its norm passes fill ([0, n): `used` of them
+  // handed out, the rest stay zero), the resources they write, and the Adam passes waiting for OP_CLIP.
+  struct ClipGroup {
+    int opt = 0;             // 0 critics, 1 policy, 2 TD7 encoder (clip_buf / rle_grad_clip_stats order)
+    float* part = nullptr;
+    int n = 0, used = 0;
+    std::vector<int> part_ids;
+    const float* gin = nullptr;  // offline TD3's actor: lmbda, in the norm passes and in OP_CLIP's scalar
+    int gin_id = -1;
+    struct Pending {
+      Op op;
+      std::vector<int> rd, wr;
+    };
+    std::vector<Pending> adam;
+  };
+  // (null with clipping off: the builders then emit the unclipped program op for op)
+  ClipGroup clip_group(int opt, const std::vector<const Layer*>& layers, float* part = nullptr) {
+    ClipGroup c;
+    c.opt = opt;
+    for (const Layer* L : layers) c.n += dw_gsq_w(*L) + dw_gsq_b(*L);
+    c.part = part ? part : mem.make<float>((size_t)c.n);
+    return c;
+  }
+  void clip_close(Prog& pg, ClipGroup& c) {
+    REQUIRE(clip_on() && !c.adam.empty() && c.used <= c.n, "clip_close: an empty or overfull clip group");
+    Op op{};
+    op.kind = OP_CLIP;
+    op.wg_count = 1;
+    ClipArgs& a = op.clip;
+    a.part = c.part;
+    a.n = c.n;
+    a.max_norm = clip_max;
+    a.gin = c.gin;
+    a.out = clip_buf + 4 * c.opt;
+    a.scale = clip_buf + 4 * c.opt + 2;
+    std::vector<int> rd = c.part_ids;
+    if (c.gin) rd.push_back(c.gin_id);
+    pg.add(op, rd, {clip_id[c.opt]});
+    for (ClipGroup::Pending& p : c.adam) pg.add(p.op, p.rd, p.wr);
+    c.adam.clear();
+  }
   struct DwOpt {
     float* gsq = nullptr;    // per-tile grad-square partials of the weights / the bias (dw_gsq_w / dw_gsq_b slots)
     float* gsq_b = nullptr;
@@ -1222,6 +1275,10 @@ struct Engine {
     DwOpt& nb_defer(const View* x) { return nb_x = x, *this; }
     DwOpt& polyak(float tau) { return ptau = tau, *this; }
     DwOpt& grad_scale(const float* s, int id) { return gscale = s, gscale_id = id, *this; }
+    // (gradient clipping) the optimizer's clip group: dw() emits the norm pass and leaves the Adam pass with the
+    // group, which clip_close() emits behind the group's OP_CLIP
+    ClipGroup* clip = nullptr;
+    DwOpt& clip_in(ClipGroup* g) { return clip = g, *this; }
   };
   struct NormBwdOpt {
     bool n = true, t = true;  // output images, as DxOpt's
@@ -1627,6 +1684,39 @@ struct Engine {
       rd.push_back(dz.nbdot_id);
     }
     op.wg_count = g.tiles_m * g.tiles_n;
+    if (ClipGroup* const c = o.clip) {
+      // Clipped: the norm pass now -- the same op (operands, tile plan, so the same accumulators) with the EPI_GSQ
+      // epilogue, which reads no parameter and writes the tile partials alone -- and the Adam pass, in its kDwGs
+      // form on the clip group's scalar, once clip_close() has emitted the group's OP_CLIP.
+      REQUIRE(!nb_x, "dw: a clipped weight gradient takes no deferred AvgL1Norm backward");
+      REQUIRE((o.gscale != nullptr) == (c->gin != nullptr), "dw: the clip group carries the gradient scale");
+      Op np = op;
+      GemmArgs& ng = np.gemm;
+      ng.epi = EPI_GSQ;
+      ng.adam.ptau = 0.f;
+      if (!o.gsq) {  // (slots of the group's own array; the TD3 actor passes norm/policy's)
+        const int nw = dw_gsq_w(L), nb = dw_gsq_b(L);
+        REQUIRE(c->used + nw + nb <= c->n, "dw: clip group partial slots");
+        ng.adam.gsq = c->part + c->used;
+        ng.adam.gsq_b = c->part + c->used + nw;
+        c->used += nw + nb;
+      }
+      std::vector<int> nrd;
+      for (int r : rd)
+        if (r != L.res && r != R_ADAMSC && r != R_ADAMSC1) nrd.push_back(r);
+      const int pid = next_id++;
+      c->part_ids.push_back(pid);
+      pg.add(np, nrd, {pid});
+      g.act = kDwGs;
+      g.gscale = clip_buf + 4 * c->opt + 2;
+      ad.gsq = ad.gsq_b = nullptr;
+      std::vector<int> ard;
+      for (int r : rd)
+        if (!o.gscale || r != o.gscale_id) ard.push_back(r);
+      ard.push_back(clip_id[c->opt]);
+      c->adam.push_back({op, ard, wr});
+      return;
+    }
     pg.add(op, rd, wr);
   }
 
@@ -2220,6 +2310,13 @@ struct Engine {
   bool offline() const { return algo == RLE_TD7 && cfg.bc_lambda > 0.f; }
   float bc_alpha = 0.f;
   bool offline3() const { return algo == RLE_TD3 && bc_alpha > 0.f; }
+  static std::vector<const Layer*> layer_ptrs(const Net& a, const Net* b = nullptr) {
+    std::vector<const Layer*> v;
+    for (const Layer& L : a.layers) v.push_back(&L);
+    if (b)
+      for (const Layer& L : b->layers) v.push_back(&L);
+    return v;
+  }
   // offline SAC (rle_config_ext awac_lambda > 0, AWAC; the temperature is fixed at 0)
   float awac_lambda = 0.f;
   bool offline_sac() const { return algo == RLE_SAC && awac_lambda > 0.f; }
@@ -2240,19 +2337,24 @@ struct Engine {
     View ea2 = fwd(pg, enc.layers[4], {{ea1}}, B, actE, FwdOpt().keep_pre(&ea2z));
     const float mean = 1.f / (float)((long long)Bv * Z);  // (mean over the B x zs_dim zsa, td7.py:253)
     View ed3 = fwd(pg, enc.layers[5], {{ea2}}, B, ACT_NONE, FwdOpt().mse(&ezs2, mean, &sb.enc_loss));
+    // (gradient clipping: optim_encoder's clip group; null when off, and every dw() below is then the op it was)
+    ClipGroup cgs;
+    if (clip_on()) cgs = clip_group(2, layer_ptrs(enc));
+    const DwOpt eo = DwOpt().clip_in(clip_on() ? &cgs : nullptr);
     View d2 = dx(pg, {{ed3, &enc.layers[5], 0}}, H, B, actE, &ea2z);
-    dw(pg, enc.layers[5], ed3, {ea2}, B, CNT_ADAM_ENC, cfg.policy_lr);
+    dw(pg, enc.layers[5], ed3, {ea2}, B, CNT_ADAM_ENC, cfg.policy_lr, eo);
     View d1 = dx(pg, {{d2, &enc.layers[4], 0}}, H, B, actE, &ea1z);
-    dw(pg, enc.layers[4], d2, {ea1}, B, CNT_ADAM_ENC, cfg.policy_lr);
+    dw(pg, enc.layers[4], d2, {ea1}, B, CNT_ADAM_ENC, cfg.policy_lr, eo);
     View gzs = dx(pg, {{d1, &enc.layers[3], 0}}, Z, B, DxOpt().no_t());  // (read by the norm backward only)
-    dw(pg, enc.layers[3], d1, {ezs, act_in}, B, CNT_ADAM_ENC, cfg.policy_lr);
+    dw(pg, enc.layers[3], d1, {ezs, act_in}, B, CNT_ADAM_ENC, cfg.policy_lr, eo);
     View dx3 = normbwd(pg, gzs, ex3.sub(0, B));
     View ez2s = ez2.sub(0, B), ez1s = ez1.sub(0, B);
     View dh2 = dx(pg, {{dx3, &enc.layers[2], 0}}, H, B, actE, &ez2s);
-    dw(pg, enc.layers[2], dx3, {eh2.sub(0, B)}, B, CNT_ADAM_ENC, cfg.policy_lr);
+    dw(pg, enc.layers[2], dx3, {eh2.sub(0, B)}, B, CNT_ADAM_ENC, cfg.policy_lr, eo);
     View dh1 = dx(pg, {{dh2, &enc.layers[1], 0}}, H, B, actE, &ez1s);
-    dw(pg, enc.layers[1], dh2, {eh1.sub(0, B)}, B, CNT_ADAM_ENC, cfg.policy_lr);
-    dw(pg, enc.layers[0], dh1, {sb.s}, B, CNT_ADAM_ENC, cfg.policy_lr);
+    dw(pg, enc.layers[1], dh2, {eh1.sub(0, B)}, B, CNT_ADAM_ENC, cfg.policy_lr, eo);
+    dw(pg, enc.layers[0], dh1, {sb.s}, B, CNT_ADAM_ENC, cfg.policy_lr, eo);
+    if (clip_on()) clip_close(pg, cgs);
   }
   // Fixed encoder on s, fixed target encoder on s', and the actor on [s; s'] (the target policy aliases the
   // policy, Q1).  The later phases read:
@@ -2382,21 +2484,25 @@ struct Engine {
   // Critic backward + Adam (optim_q_fns spans q1 + q2)
   void td7_critic_backward(Prog& pg, const StepBuild& sb, const Td7Actor& ac, const Td7Critics& cr) {
     const bool nbd = td7_nb_defer();
+    ClipGroup cgs;  // (gradient clipping: optim_q_fns' clip group, q1 + q2 together)
+    if (clip_on()) cgs = clip_group(0, layer_ptrs(net("q1"), &net("q2")));
+    const DwOpt qo = DwOpt().clip_in(clip_on() ? &cgs : nullptr);
     for (int n = 0; n < 2; ++n) {
       Net& Q = net(n ? "q2" : "q1");
-      dw(pg, Q.layers[3], cr.dq[n], {cr.c2[n]}, B, CNT_ADAM_Q, cfg.critic_lr);
+      dw(pg, Q.layers[3], cr.dq[n], {cr.c2[n]}, B, CNT_ADAM_Q, cfg.critic_lr, qo);
       View d1 = cr.hdx ? cr.d1f[n] : dx(pg, {{cr.dz2[n], &Q.layers[2], 0}}, H, B, actC, &cr.c1z[n]);
-      dw(pg, Q.layers[2], cr.dz2[n], {cr.c1[n]}, B, CNT_ADAM_Q, cfg.critic_lr);
+      dw(pg, Q.layers[2], cr.dz2[n], {cr.c1[n]}, B, CNT_ADAM_Q, cfg.critic_lr, qo);
       // (read by the weight gradient / the norm backward only: the T / the N image alone)
       View g01 = dx(pg, {{d1, &Q.layers[1], 0}}, H, B, DxOpt().nb_defer(nbd ? &cr.c01[n] : nullptr).images(!nbd, nbd));
-      dw(pg, Q.layers[1], d1, {cr.c01[n], ac.fzsa, ac.fzs}, B, CNT_ADAM_Q, cfg.critic_lr);
+      dw(pg, Q.layers[1], d1, {cr.c01[n], ac.fzsa, ac.fzs}, B, CNT_ADAM_Q, cfg.critic_lr, qo);
       if (nbd) {  // AvgL1Norm backward deferred into the weight-gradient GEMM (kDwNb)
         dw(pg, Q.layers[0], g01, {sb.s, act_in}, B, CNT_ADAM_Q, cfg.critic_lr, DwOpt().nb_defer(&cr.c01[n]));
       } else {
         View dx01 = normbwd(pg, g01, cr.c01[n]);
-        dw(pg, Q.layers[0], dx01, {sb.s, act_in}, B, CNT_ADAM_Q, cfg.critic_lr);
+        dw(pg, Q.layers[0], dx01, {sb.s, act_in}, B, CNT_ADAM_Q, cfg.critic_lr, qo);
       }
     }
+    if (clip_on()) clip_close(pg, cgs);
   }
   // Upper bound on the tiles of an EPI_QHEAD GEMM over B rows (its loss partial slots).
   int qhead_tiles(const Layer& L) const { return cdiv(B, kTileM) * cdiv(L.out, kTileM); }
@@ -2473,18 +2579,22 @@ struct Engine {
     const View ap2zs = act_zsaved(actP) ? ac.ap2z.sub(0, B) : View{}, ap1zs = act_zsaved(actP) ? ac.ap1z.sub(0, B) : View{};
     View dl2 = dx(pg, {{dl3, &pi.layers[3], 0}}, H, B, actP, dsrc_of(actP, ap2s, ap2zs),
                   DxOpt().pre_gemm(ac.prea ? &p3 : nullptr));
-    dw(pg, pi.layers[3], dl3, {ap2s}, B, CNT_ADAM_PI, cfg.policy_lr);
+    ClipGroup cgs;  // (gradient clipping: optim_policy's clip group)
+    if (clip_on()) cgs = clip_group(1, layer_ptrs(pi));
+    const DwOpt pio = DwOpt().clip_in(clip_on() ? &cgs : nullptr);
+    dw(pg, pi.layers[3], dl3, {ap2s}, B, CNT_ADAM_PI, cfg.policy_lr, pio);
     View dl1 = dx(pg, {{dl2, &pi.layers[2], 0}}, H, B, actP, dsrc_of(actP, ap1s, ap1zs));
-    dw(pg, pi.layers[2], dl2, {ap1s}, B, CNT_ADAM_PI, cfg.policy_lr);
+    dw(pg, pi.layers[2], dl2, {ap1s}, B, CNT_ADAM_PI, cfg.policy_lr, pio);
     const View ap0s = ac.ap0.sub(0, B);
     View gl0 = dx(pg, {{dl1, &pi.layers[1], 0}}, H, B, DxOpt().nb_defer(nbd ? &ap0s : nullptr).images(!nbd, nbd));
-    dw(pg, pi.layers[1], dl1, {ap0s, fzs}, B, CNT_ADAM_PI, cfg.policy_lr);
+    dw(pg, pi.layers[1], dl1, {ap0s, fzs}, B, CNT_ADAM_PI, cfg.policy_lr, pio);
     if (nbd) {
       dw(pg, pi.layers[0], gl0, {s}, B, CNT_ADAM_PI, cfg.policy_lr, DwOpt().nb_defer(&ap0s));
     } else {
       View dl0 = normbwd(pg, gl0, ap0s);
-      dw(pg, pi.layers[0], dl0, {s}, B, CNT_ADAM_PI, cfg.policy_lr);
+      dw(pg, pi.layers[0], dl0, {s}, B, CNT_ADAM_PI, cfg.policy_lr, pio);
     }
+    if (clip_on()) clip_close(pg, cgs);
   }
   // Step end: info row [encoder, q_fn, policy] (offline: + [bc, q_abs])
   void td7_step_end(Prog& pg, const StepBuild& sb) {
@@ -2808,19 +2918,23 @@ struct Engine {
   // Critic backward + Adam (input gradients through a layer before its Adam update)
   void mlp_critic_backward(Prog& pg, const StepBuild& sb, const MlpCritics& cr) {
     const int D = (int)HS.size();
+    ClipGroup cgs;  // (gradient clipping: the critics' optimizer, q1 + q2 together)
+    if (clip_on()) cgs = clip_group(0, layer_ptrs(net("q1"), &net("q2")));
+    const DwOpt qo = DwOpt().clip_in(clip_on() ? &cgs : nullptr);
     for (int n = 0; n < 2; ++n) {
       Net& Q = net(n ? "q2" : "q1");
-      dw(pg, Q.layers[D], cr.dq[n], {cr.c[n][D - 1]}, B, CNT_ADAM_Q, cfg.critic_lr);
+      dw(pg, Q.layers[D], cr.dq[n], {cr.c[n][D - 1]}, B, CNT_ADAM_Q, cfg.critic_lr, qo);
       View d = cr.dz1[n];  // dZ of hidden layer i, from i = D - 1 down
       for (int i = D - 1; i >= 1; --i) {
         const View dp = cr.hdx && i == D - 1 ? cr.d0f[n]
                                               : dx(pg, {{d, &Q.layers[i], 0}}, HS[i - 1], B, actC,
                                                    dsrc_of(actC, cr.c[n][i - 1], cr.cz[n][i - 1]));
-        dw(pg, Q.layers[i], d, {cr.c[n][i - 1]}, B, CNT_ADAM_Q, cfg.critic_lr);
+        dw(pg, Q.layers[i], d, {cr.c[n][i - 1]}, B, CNT_ADAM_Q, cfg.critic_lr, qo);
         d = dp;
       }
-      dw(pg, Q.layers[0], d, {sb.s, act_in}, B, CNT_ADAM_Q, cfg.critic_lr);
+      dw(pg, Q.layers[0], d, {sb.s, act_in}, B, CNT_ADAM_Q, cfg.critic_lr, qo);
     }
+    if (clip_on()) clip_close(pg, cgs);
   }
   // Policy pass through the updated critics, the objective's head, the actor's backward + Adam
   void mlp_policy(Prog& pg, StepBuild& sb, const MlpActor& ac) {
@@ -3004,11 +3118,19 @@ struct Engine {
     for (int i = 0; i < D; ++i) hsub[i] = ac.h[i].sub(0, B);
     if (pz)
       for (int i = 0; i < D; ++i) hzsub[i] = ac.hz[i].sub(0, B);
+    // Gradient clipping: the policy optimizer's clip group.  TD3: over norm/policy's partial slots, which the norm
+    // passes then fill (the gradient before clipping; offline with lmbda) and OP_CLIP adds as well
+    ClipGroup cgs;
+    if (clip_on()) {
+      cgs = clip_group(1, layer_ptrs(pi), sb.gsq);
+      if (offline3()) cgs.gin = sb.bc_s + 1, cgs.gin_id = sb.bc_s_id;
+    }
     // What every weight gradient of the actor shares.  TD3: the aliased target policy's Polyak (td3.py:200-204)
     // in the Adam epilogues: one level fewer between the actor update and the next step's target action.
     // Offline TD3: the gradient scaled by lmbda (sb.bc_s[1])
     const DwOpt ao = DwOpt().polyak(!sac && pi_polyak_fused() ? cfg.tau : 0.f)
-                         .grad_scale(offline3() ? sb.bc_s + 1 : nullptr, sb.bc_s_id);
+                         .grad_scale(offline3() ? sb.bc_s + 1 : nullptr, sb.bc_s_id)
+                         .clip_in(clip_on() ? &cgs : nullptr);
     // SAC: d1 (the gradient through the raw head, K = 2A <= 48) recomputed in-tile by d0's DX
     const bool pld = sac && sac_bwd_fused() && prelayer_ok_dx(Lout, pi.layers[D - 1]);
     View d = dx(pg, {{dout, &Lout, 0}}, HS[D - 1], B, actP, dsrc_of(actP, hsub[D - 1], hzsub[D - 1]),
@@ -3027,6 +3149,7 @@ struct Engine {
       d = dp;
     }
     dw(pg, pi.layers[0], d, {s}, B, CNT_ADAM_PI, cfg.policy_lr, DwOpt(ao).gsq_parts(gl[0]));
+    if (clip_on()) clip_close(pg, cgs);
     if (sb.gsq) {
       // tensor t owns tiles [gsq_offs[t], gsq_offs[t+1]) (params() order: w0, b0, w1, b1, ...)
       sb.gsq_offs.assign(1, 0);
@@ -3156,12 +3279,14 @@ struct Engine {
       }
       for (size_t k = 0; k < levels[l].size(); ++k) {
         const Op& op = levels[l][k];
-        G.desc += std::string(" ") + (pg.crit_lv[l][k] ? "*" : "") + (op.kind == OP_AWAC ? "awac" : kname[op.kind]);
+        G.desc += std::string(" ") + (pg.crit_lv[l][k] ? "*" : "") +
+                  (op.kind == OP_AWAC ? "awac" : op.kind == OP_CLIP ? "clip" : kname[op.kind]);
         if (op.kind == OP_GEMM) {
-          static const char* kepi[] = {"st", "adam", "mse", "qhead", "nbdot", "act", "qdot", "sacbwd", "sacfwd"};
-          static_assert(sizeof(kepi) / sizeof(kepi[0]) == EPI_SACFWD + 1, "every epilogue has a name");
+          static const char* kepi[] = {"st", "adam", "mse", "qhead", "nbdot", "act", "qdot", "sacbwd", "sacfwd", "gsq"};
+          static_assert(sizeof(kepi) / sizeof(kepi[0]) == EPI_GSQ + 1, "every epilogue has a name");
           // (adam+nbr: the dot partials row-major, RLE_FUSE_NBROWS)
           const char* ep = op.gemm.mode == GEMM_DW && op.gemm.act == kDwNb ? (op.gemm.nbdot_ld < 0 ? "adam+nbr" : "adam+nb")
+                           : op.gemm.epi == EPI_GSQ ? (op.gemm.act == kDwGs ? "gsq+gs" : "gsq")  // (the norm pass)
                            : op.gemm.mode == GEMM_DW && op.gemm.act == kDwGs ? "adam+gs"
                            : op.gemm.has_pre == 2                         ? "head+dx"
                            : op.gemm.has_pre == 3                         ? (op.gemm.epi == EPI_QDOT ? "qdot+pl" : "st+pl")
@@ -3186,7 +3311,7 @@ struct Engine {
         REQUIRE(op.kind != OP_GEMM || gemm_variant_compiled(op.gemm.vid, kernel_set()),
                 "capture: a GEMM variant outside the engine's rle_level instance (ops.h RLE_GEMM_VARIANTS sets)");
         // (LeakyReLU / SiLU / GELU: the second dispatch under the ELU ids is the KS_ACT instance's alone)
-        REQUIRE(kernel_set() == KS_ACT ||
+        REQUIRE(ks_act_rt(kernel_set()) ||
                     ((op.kind != OP_GEMM || op.gemm.mode == GEMM_DW ||
                       (op.gemm.mode == GEMM_FWD ? op.gemm.act : op.gemm.dact) <= ACT_TANH) &&
                      (op.kind != OP_HEAD || op.head.dact <= ACT_TANH)),
@@ -3300,7 +3425,7 @@ struct Engine {
       if (op.kind != OP_GEMM) return op.wg_count;
       const GemmArgs& g = op.gemm;
       if (g.hot.wide) return op.wg_count;  // (64-row tiles: never widened)
-      return g.tiles_m * (cdiv(g.N, at(op.seq)) + (g.epi == EPI_ADAM ? 1 : 0));
+      return g.tiles_m * (cdiv(g.N, at(op.seq)) + (g.epi == EPI_ADAM || g.epi == EPI_GSQ ? 1 : 0));
     };
     for (auto& lv : levels) {
       while (true) {
@@ -3341,6 +3466,12 @@ struct Engine {
     ensure_tapes(1024);
     const bool sac = algo == RLE_SAC;
     alloc_folds();
+    if (clip_on() && !clip_buf) {  // ({total, coef} read NaN until an optimizer's first clipped update)
+      clip_buf = mem.make<float>(12);
+      std::vector<float> nan(12, std::numeric_limits<float>::quiet_NaN());
+      HIPCHK(hipMemcpy(clip_buf, nan.data(), sizeof(float) * 12, hipMemcpyHostToDevice));
+      for (int& id : clip_id) id = next_id++;
+    }
     multi_k = pair_k();
     // K steps from batch set `set` on, as one program.  TD7 / TD3: policy, plain, ...; SAC: every step is a policy step
     auto steps = [&](int set, int K, bool first_policy) {
@@ -4343,6 +4474,39 @@ int rle_set_plan(rle_engine* h, const rle_plan* plan) {
     REQUIRE(!e.built, "set_plan: the engine has already built its step programs (set the plan before the first step)");
     e.plan = *plan;
     e.resolve_plan();
+  });
+}
+
+int rle_set_grad_clip(rle_engine* h, float max_norm) {
+  return guard([&] {
+    REQUIRE(h, "set_grad_clip: null");
+    REQUIRE(max_norm >= 0.f, "set_grad_clip: max_norm must be >= 0 (0 or +inf: off)");  // (NaN fails too)
+    Engine& e = drained(h);
+    if (e.built)
+      throw Error{RLE_ESTATE, "set_grad_clip: the engine has already built its step programs (set it before the "
+                              "first step)"};
+    e.clip_max = std::isinf(max_norm) ? 0.f : max_norm;
+  });
+}
+
+int rle_get_grad_clip(rle_engine* h, float* max_norm) {
+  return guard([&] {
+    REQUIRE(h && max_norm, "get_grad_clip: null");
+    *max_norm = h->e->clip_max;
+  });
+}
+
+int rle_grad_clip_stats(rle_engine* h, float* out6) {
+  return guard([&] {
+    REQUIRE(h && out6, "grad_clip_stats: null");
+    Engine& e = drained(h);
+    for (int i = 0; i < 6; ++i) out6[i] = std::numeric_limits<float>::quiet_NaN();
+    if (!e.clip_buf) return;
+    HIPCHK(hipSetDevice(e.cfg.device));
+    HIPCHK(hipStreamSynchronize(e.stream));
+    float b[12];
+    HIPCHK(hipMemcpy(b, e.clip_buf, sizeof b, hipMemcpyDeviceToHost));
+    for (int o = 0; o < 3; ++o) out6[2 * o] = b[4 * o], out6[2 * o + 1] = b[4 * o + 1];
   });
 }
 

@@ -1615,7 +1615,7 @@ __device__ __forceinline__ void gemm_v(const CAS GemmArgs& g, int t, float* smem
   if constexpr (MODE == GEMM_DW) {
     if (tn == 64) __builtin_amdgcn_s_setprio(3);
   }
-  const bool bias_tile = EPI == EPI_ADAM && jt * tn >= bias_col;
+  const bool bias_tile = (EPI == EPI_ADAM || EPI == EPI_GSQ) && jt * tn >= bias_col;
   const bool lead = kp == 0;
   const bool active = bias_tile ? cg == 0 : j0 < gN;  // wave-uniform
   const int j = j0 + (lane & 15), ib = i0 + ((lane >> 4) << 2);
@@ -1662,7 +1662,9 @@ __device__ __forceinline__ void gemm_v(const CAS GemmArgs& g, int t, float* smem
         sfe[k] = b < s.eps_row_split ? mat_ld(s.eps2, b, jj) : mat_ld(s.eps, b - s.eps_row_split, jj);
     }
   }
-  if constexpr (EPI != EPI_ADAM) {
+  if constexpr (EPI == EPI_GSQ) {
+    // (the norm pass loads no parameter, moment or bias)
+  } else if constexpr (EPI != EPI_ADAM) {
     if (jok && biasp) pre_b = G(biasp)[j];
     if constexpr (MODE == GEMM_DX && ACT != ACT_NONE) {
       if (jok) ds = mat_ld4(g.dsrc, ib, j);
@@ -2214,6 +2216,24 @@ __device__ __forceinline__ void gemm_v(const CAS GemmArgs& g, int t, float* smem
     }
     d2 = wg_sum(d2, red);
     if (tid == 0) GW(g.loss_part)[it * tiles_n + jt] = d2;  // (by tile: see EPI_QHEAD)
+  } else if constexpr (EPI == EPI_GSQ) {  // norm pass of a clipped optimizer: EPI_ADAM's gsq partial and nothing else
+    const CAS AdamArgs& ad = g.adam;
+    float gg = 0.f;
+    if (jok) {
+      constexpr bool GSC = ACT == kDwGs;  // (offline TD3's lmbda, multiplied in before squaring as EPI_ADAM does)
+      float gs = 1.f;
+      if constexpr (GSC) gs = sload(g.gscale);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float gv = GSC ? acc[q] * gs : acc[q];
+        gg += ib + q < g.M ? gv * gv : 0.f;  // (weight rows past out: no gradient)
+      }
+    }
+    gg = wg_sum(gg, red);
+    if (tid == 0) {
+      if (bias_tile) GW(ad.gsq_b)[it] = gg;
+      else GW(ad.gsq)[it * (tiles_n - 1) + jt] = gg;
+    }
   } else {  // EPI_ADAM (torch.optim.Adam single-tensor law, see oracle/agents.py)
     const CAS AdamArgs& ad = g.adam;
     float gg = 0.f;
@@ -2285,7 +2305,7 @@ __device__ __forceinline__ void op_gemm(const CAS GemmArgs& g, int vid, int t, f
   constexpr bool XS = ks_family(KS) == KS_EXT;  // (the extended instance or KS_ACT: every variant)
 #define RLE_VX(mode, epi, act, norm, pre, pk, sets)                                                       \
   case gemm_vid(mode, epi, act, norm, pre):                                                               \
-    if constexpr (KS == KS_ACT && mode != GEMM_DW && act == ACT_ELU && ((pk) == 0 || (pk) == 2)) {        \
+    if constexpr (ks_act_rt(KS) && mode != GEMM_DW && act == ACT_ELU && ((pk) == 0 || (pk) == 2)) {      \
       if (art > ACT_TANH) {                                                                               \
         asm volatile("; gemm variant " #mode " " #epi " kActRt norm " #norm " pk " #pk ::);               \
         gemm_v<mode, epi, mode != GEMM_DW && act == ACT_ELU ? kActRt : act, (norm) != 0 && (pk) <= 3, pk, \
@@ -2293,7 +2313,7 @@ __device__ __forceinline__ void op_gemm(const CAS GemmArgs& g, int vid, int t, f
         break;                                                                                            \
       }                                                                                                   \
     }                                                                                                     \
-    if constexpr (XS || (((sets) >> ks_family(KS)) & 1)) {                                                \
+    if constexpr (variant_in_set(sets, KS)) {                                                             \
       asm volatile("; gemm variant " #mode " " #epi " " #act " norm " #norm " pk " #pk ::);               \
       gemm_v<mode, epi, act, (norm) != 0 && (pk) <= 3, pk, XS || KS == KS_TD7W,                           \
              (KS == KS_TD7W || XS) && wide_variant(mode, epi, pk)>(g, t, smem, tr);                       \
@@ -3363,6 +3383,23 @@ __device__ __forceinline__ void op_awac(const CAS AwacArgs& s, int t, float* sme
   }
 }
 
+// ---------------------------------------------------------------- gradient clipping (ops.h ClipArgs)
+// One workgroup: the optimizer's global gradient norm from its norm passes' per-tile partials and the clip
+// coefficient of torch.nn.utils.clip_grad_norm_ (a NaN or inf norm propagates: no fminf, which would drop a NaN).
+__device__ __forceinline__ void op_clip(const CAS ClipArgs& c, float* smem) {
+  const int tid = threadIdx.x;
+  float s = 0.f;
+  for (int i = tid; i < c.n; i += kThreads) s += G(c.part)[i];
+  const float total = sqrtf(wg_sum(s, smem));
+  if (tid == 0) {
+    const float r = __fdiv_rn(c.max_norm, __fadd_rn(total, 1e-6f));
+    const float coef = r > 1.f ? 1.f : r;
+    GW(c.out)[0] = total;
+    GW(c.out)[1] = coef;
+    GW(c.scale)[0] = c.gin ? __fmul_rn(G(c.gin)[0], coef) : coef;
+  }
+}
+
 // ---------------------------------------------------------------- dispatch
 
 // TRACE: compiled with the phase stamps (RLE_TRACE=1 runs); the production instance has
@@ -3453,7 +3490,7 @@ __global__ __launch_bounds__(kThreads, RLE_WAVES) void rle_level(unsigned e0, un
     RLE_OP(OP_NORMBWD, op_normbwd(op.nb, t))
     RLE_OP(OP_SAMPLE_REDUCE, op_sample_reduce(op.sample, t, smem))
     RLE_OP(OP_SAMPLE_GATHER, op_sample_gather<ks_family(KS) == KS_EXT>(op.sample, t, smem, tr))
-    RLE_OP(OP_HEAD, (op_head<ks_family(KS) == KS_EXT, KS == KS_ACT>(op.head, t, smem, tr)))
+    RLE_OP(OP_HEAD, (op_head<ks_family(KS) == KS_EXT, ks_act_rt(KS)>(op.head, t, smem, tr)))
     RLE_OP(OP_PRIORITY, op_priority(op.prio, smem))
     RLE_OP(OP_SAC_ACTOR, op_sac_actor(op.sac, t))
     RLE_OP(OP_SAC_ACTOR_BWD, op_sac_actor_bwd(op.sac, t))
@@ -3467,13 +3504,18 @@ __global__ __launch_bounds__(kThreads, RLE_WAVES) void rle_level(unsigned e0, un
     // (kinds past 15, ops.h OpKind: low bits 0, kind >> 4 in the variant field; the TD7 family's instances)
     // (OP_AWAC, offline SAC: the extended instance's alone)
     RLE_OP(0, if (ks_family(KS) != KS_MLP && vid == (OP_BC >> 4)) op_bc<ks_family(KS) == KS_EXT>(op.bc, t, smem);
-           else if (ks_family(KS) == KS_EXT && vid == (OP_AWAC >> 4)) op_awac(op.awac, t, smem))
+           else if (ks_family(KS) == KS_EXT && vid == (OP_AWAC >> 4)) op_awac(op.awac, t, smem);
+           else if (KS == KS_CLIP && vid == (OP_CLIP >> 4)) op_clip(op.clip, smem))
 #undef RLE_OP
     default: break;
   }
   trace_mark(tr, 3);
 }
 
+// clip_level.hip compiles this file up to here (RLE_CLIP_TU) for the KS_CLIP instance alone: a code object of its
+// own, so this translation unit's -- every other instance and the stand-alone kernels below -- is the one it was
+// before clipped programs existed, down to the kernels' addresses.
+#ifndef RLE_CLIP_TU
 
 // ---------------------------------------------------------------- B = 1 act chain (ops.h ActChainArgs)
 // Row block rb of layer L in registers: column block cb = wave + 4 i of the [16][K] strip, lane l
@@ -3958,23 +4000,28 @@ int trace_stride() { return kTraceStride; }
   X(KS_EXT, "_ZN3rle9rle_levelILb0ELi2EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd")  \
   X(KS_TD7W, "_ZN3rle9rle_levelILb0ELi3EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd") \
   X(KS_ACT, "_ZN3rle9rle_levelILb0ELi4EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd")
+// (KS_CLIP: the last KernelSet, instantiated in clip_level.hip)
+const void* clip_level_fn(int traced);
+constexpr const char* kClipLevelSymbol = "_ZN3rle9rle_levelILb0ELi5EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd";
+constexpr int kLevelRows = KS_CLIP;  // instances of this translation unit
 #define RLE_ROW_KS(KS, sym) KS,
 #define RLE_ROW_FN(KS, sym) (const void*)rle_level<false, KS>,
 #define RLE_ROW_FN_TRACED(KS, sym) (const void*)rle_level<true, KS>,
 #define RLE_ROW_SYMBOL(KS, sym) sym,
 static const struct {
-  const void* fn[2][KS_COUNT];  // [traced][ks]
-  const char* symbol[KS_COUNT];
+  const void* fn[2][kLevelRows];  // [traced][ks]
+  const char* symbol[kLevelRows];
 } kLevel = {{{RLE_LEVEL_INSTANCES(RLE_ROW_FN)}, {RLE_LEVEL_INSTANCES(RLE_ROW_FN_TRACED)}},
             {RLE_LEVEL_INSTANCES(RLE_ROW_SYMBOL)}};
 constexpr int kLevelRowKs[] = {RLE_LEVEL_INSTANCES(RLE_ROW_KS)};
 constexpr bool level_rows_follow_enum() {
-  for (int i = 0; i < KS_COUNT; ++i)
+  for (int i = 0; i < kLevelRows; ++i)
     if (kLevelRowKs[i] != i) return false;
   return true;
 }
-static_assert(sizeof(kLevelRowKs) == KS_COUNT * sizeof(int) && level_rows_follow_enum(),
-              "RLE_LEVEL_INSTANCES: one row per KernelSet, in the enum's order");
+static_assert(sizeof(kLevelRowKs) == kLevelRows * sizeof(int) && level_rows_follow_enum() && KS_CLIP + 1 == KS_COUNT,
+              "RLE_LEVEL_INSTANCES: one row per KernelSet but the last, in the enum's order");
+static const void* level_fn(int traced, int ks) { return ks == KS_CLIP ? clip_level_fn(traced) : kLevel.fn[traced][ks]; }
 #undef RLE_ROW_KS
 #undef RLE_ROW_FN
 #undef RLE_ROW_FN_TRACED
@@ -3985,16 +4032,16 @@ static_assert(sizeof(kLevelRowKs) == KS_COUNT * sizeof(int) && level_rows_follow
 int level_capacity() {
   int per_cu = 1 << 30, cus = 0, dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 1024;
-  for (const void* fn : kLevel.fn[0]) {
+  for (int ks = 0; ks < KS_COUNT; ++ks) {  // (this also loads every instance's code object: dispatch.cpp aql_hw_create)
     int p = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&p, fn, kThreads, 0) != hipSuccess) return 1024;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&p, level_fn(0, ks), kThreads, 0) != hipSuccess) return 1024;
     per_cu = per_cu < p ? per_cu : p;
   }
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 1024;
   return per_cu * cus;
 }
 
-const char* level_kernel_symbol(int ks) { return kLevel.symbol[ks]; }
+const char* level_kernel_symbol(int ks) { return ks == KS_CLIP ? kClipLevelSymbol : kLevel.symbol[ks]; }
 
 // Launches the instance the packet names with the packet's own argument bytes.
 hipError_t launch_packet(const LevelLaunch& L, hipStream_t st) {
@@ -4006,7 +4053,7 @@ hipError_t launch_packet(const LevelLaunch& L, hipStream_t st) {
   args[kLevelOps + 1] = &ka.trace;
   args[kLevelOps + 2] = &ka.next;
   args[kLevelOps + 3] = &ka.next_lines;
-  return hipLaunchKernel(kLevel.fn[L.traced][L.ks], dim3(L.grid), dim3(kThreads), args, 0, st);
+  return hipLaunchKernel(level_fn(L.traced, L.ks), dim3(L.grid), dim3(kThreads), args, 0, st);
 }
 hipError_t launch_append(float* state, float* next_state, float* action, float* reward, float* notdone,
                          float* priority, const float* st_s, const float* st_ns, const float* st_a,
@@ -4063,5 +4110,13 @@ hipError_t launch_fill(float* state, float* next_state, float* action, float* re
                      notdone, priority, n, S, Sp, A, Ap, seed);
   return hipGetLastError();
 }
+
+#else  // RLE_CLIP_TU
+
+const void* clip_level_fn(int traced) {
+  return traced ? (const void*)rle_level<true, KS_CLIP> : (const void*)rle_level<false, KS_CLIP>;
+}
+
+#endif  // RLE_CLIP_TU
 
 }  // namespace rle

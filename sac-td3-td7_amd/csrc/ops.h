@@ -35,6 +35,7 @@ enum OpKind : int {
   // non-GEMM op, kind >> 4 in the variant field (LevelArgs::entry), so every earlier entry is unchanged.
   OP_BC = 16,           // TD7 offline: the behaviour-cloning term's scalars and action-gradient operand (BcArgs)
   OP_AWAC = 32,         // offline SAC: the advantage-weighted policy step's row-wise op (AwacArgs; the extended instance)
+  OP_CLIP = 48,         // gradient clipping: an optimizer's global norm and clip coefficient (ClipArgs; KS_CLIP alone)
 };
 
 // ---------------------------------------------------------------- tensor images
@@ -110,6 +111,9 @@ enum Epi : int {
                    // backward (as OP_SAC_ACTOR_BWD) per element in the epilogue -> d / d(mean | log_std)
   EPI_SACFWD = 8,  // the SAC actor's raw head (tile = whole rows, tn 64 >= 2A): raw stored, then the
                    // rsample, tanh action and log pi of the tile's rows (as OP_SAC_ACTOR)
+  EPI_GSQ = 9,     // norm pass of a clipped optimizer's weight gradient (GEMM_DW): the accumulators EPI_ADAM would
+                   // take, no parameter or moment loaded, only the tile's sum of squared gradients stored
+                   // (AdamArgs::gsq / gsq_b, masked and summed as EPI_ADAM does); KS_CLIP alone
 };
 
 // Environment action of an act graph (td7.py:141-156, td3.py:114-129, sac.py:132-152), written
@@ -135,6 +139,9 @@ constexpr int kDwNb = 1;  // (in the act slot of a DW variant id)
 // GEMM_DW variant whose Adam epilogue multiplies the accumulated gradient by the device scalar GemmArgs::gscale
 // (offline TD3's lmbda) before the moments and the gsq partials.  The extended instance alone holds
 // it: offline TD3 programs run there, so the TD3 / SAC instance is the code it was for the online programs.
+// Clipped programs (rle_set_grad_clip; the KS_CLIP instance): the scalar is the optimizer's clip coefficient
+// (OP_CLIP's ClipArgs::scale; times lmbda for the offline TD3 actor), also with normed operands (TD7).  Their norm
+// pass (EPI_GSQ) takes kDwGs for offline TD3's lmbda alone, multiplied in before squaring.
 constexpr int kDwGs = 2;  // (in the act slot of a DW variant id)
 
 struct AdamArgs {
@@ -168,7 +175,8 @@ static_assert(gemm_vid(2, 8, 15, 1, 3) < 2048, "GEMM variant ids fit 11 bits");
 // extended instance holds all).  kernels.hip op_gemm dispatches exactly these, and the engine refuses a
 // program with an op whose id is not in its kernel set.  (sets 0: the extended instance only -- the TD7 policy
 // pass's q-head under a non-default critic activation, rle_config act_critic, and the offline policy pass's
-// q row partials under identity critics, rle_config bc_lambda)
+// q row partials under identity critics, rle_config bc_lambda; sets 4: the KS_CLIP instance only -- the norm pass
+// and the scaled Adam pass over normed operands of a clipped program, variant_in_set below)
 #define RLE_GEMM_VARIANTS(X)                        \
   X(GEMM_FWD, EPI_STORE, ACT_NONE, 0, 0, 0, 3)      \
   X(GEMM_FWD, EPI_STORE, ACT_NONE, 1, 0, 0, 1)      \
@@ -196,6 +204,10 @@ static_assert(gemm_vid(2, 8, 15, 1, 3) < 2048, "GEMM variant ids fit 11 bits");
   X(GEMM_DW, EPI_ADAM, ACT_NONE, 1, 0, 0, 1)        \
   X(GEMM_DW, EPI_ADAM, kDwNb, 0, 0, 0, 1)           \
   X(GEMM_DW, EPI_ADAM, kDwGs, 0, 0, 0, 0)           \
+  X(GEMM_DW, EPI_ADAM, kDwGs, 1, 0, 0, 4)           \
+  X(GEMM_DW, EPI_GSQ, ACT_NONE, 0, 0, 0, 4)         \
+  X(GEMM_DW, EPI_GSQ, ACT_NONE, 1, 0, 0, 4)         \
+  X(GEMM_DW, EPI_GSQ, kDwGs, 0, 0, 0, 4)            \
   X(GEMM_FWD, EPI_STORE, ACT_NONE, 0, 1, 1, 1)      \
   X(GEMM_FWD, EPI_STORE, ACT_RELU, 0, 1, 1, 3)      \
   X(GEMM_FWD, EPI_STORE, ACT_ELU, 1, 1, 1, 1)       \
@@ -223,9 +235,18 @@ constexpr bool wide_variant(int mode, int epi, int pk) {
 // act_vslot above), for engines with one of those activations -- a set of its own, so the extended instance,
 // which the ReLU / ELU / identity combinations outside the agents' own sets run on, is the code it was before
 // those activations existed (their erff / expf epilogues cost its ELU programs 1-2%, DESIGN "More hidden activations")
-enum KernelSet : int { KS_TD7 = 0, KS_MLP = 1, KS_EXT = 2, KS_TD7W = 3, KS_ACT = 4, KS_COUNT = 5 };
+// KS_CLIP: KS_ACT's code plus the clipped programs' own (EPI_GSQ, the sets-4 variants, OP_CLIP), for engines with
+// rle_set_grad_clip on -- a set of its own for the same reason: every other instance is the code it was.  It is
+// instantiated in clip_level.hip, a code object of its own, so the others also stay at the addresses they had.
+enum KernelSet : int { KS_TD7 = 0, KS_MLP = 1, KS_EXT = 2, KS_TD7W = 3, KS_ACT = 4, KS_CLIP = 5, KS_COUNT = 6 };
 // the agent family whose variants (RLE_GEMM_VARIANTS sets bit) and ops an instance compiles
-constexpr int ks_family(int ks) { return ks == KS_TD7W ? KS_TD7 : ks == KS_ACT ? KS_EXT : ks; }
+constexpr int ks_family(int ks) { return ks == KS_TD7W ? KS_TD7 : ks == KS_ACT || ks == KS_CLIP ? KS_EXT : ks; }
+// the instances that dispatch an ELU id a second time on the op's activation (kActRt: LeakyReLU / SiLU / GELU)
+constexpr bool ks_act_rt(int ks) { return ks == KS_ACT || ks == KS_CLIP; }
+// whether instance ks compiles a variant of RLE_GEMM_VARIANTS with this sets field
+constexpr bool variant_in_set(int sets, int ks) {
+  return (sets & 4) ? ks == KS_CLIP : ks_family(ks) == KS_EXT || ((sets >> ks_family(ks)) & 1);
+}
 
 enum GemmMode : int {
   GEMM_FWD = 0,   // A contiguous (activations), B contiguous (W rows):  Y = X W^T
@@ -619,6 +640,20 @@ struct AwacArgs {
   float lambda, min_log_std, max_log_std;
 };
 
+// Gradient clipping of one optimizer (rle_set_grad_clip; torch.nn.utils.clip_grad_norm_, error_if_nonfinite
+// False), one workgroup, between the optimizer's norm passes (EPI_GSQ) and its Adam passes (kDwGs):
+//   total = sqrt(sum of part[0 .. n)),  c = max_norm / (total + 1e-6),  coef = c > 1 ? 1 : c   (NaN stays NaN)
+//   out = {total, coef},  scale[0] = coef, or gin[0] * coef (offline TD3's actor: lmbda, which the norm pass
+//   multiplied in before squaring)
+// Summation order: thread t adds partials t, t + 256, ...; then wg_sum.  Fixed by n alone; no atomics.
+struct ClipArgs {
+  const float* part; int n;
+  float max_norm;
+  const float* gin;      // optional [1]
+  float* out;            // [2]
+  float* scale;          // [1]
+};
+
 struct FlatArgs {   // POLYAK / COPY / MAXRED
   float* dst; const float* src; long long n;
   float tau, omt; int self_alias;     // self_alias: p <- tau*p + p*(1-tau) (TD3 quirk Q2)
@@ -653,6 +688,7 @@ struct Op {
     FoldBiasArgs fb;
     BcArgs bc;
     AwacArgs awac;
+    ClipArgs clip;
   };
 };
 // kernels.hip gemm_v touches the descriptor's 64-byte lines by fixed offsets from &gemm (its

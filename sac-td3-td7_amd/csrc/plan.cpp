@@ -42,7 +42,7 @@ static void xcd_plan(GemmArgs& g, bool xcd);
 
 bool gemm_variant_compiled(int vid, int ks) {
 #define RLE_VID(mode, epi, act, norm, pre, pk, sets) \
-  (vid == gemm_vid(mode, epi, act, norm, pre) && (ks < 0 || ks_family(ks) == KS_EXT || (((sets) >> ks_family(ks)) & 1))) ||
+  (vid == gemm_vid(mode, epi, act, norm, pre) && (ks < 0 || variant_in_set(sets, ks))) ||
   return RLE_GEMM_VARIANTS(RLE_VID) false;
 #undef RLE_VID
 }
@@ -59,8 +59,13 @@ void gemm_finalize(GemmArgs& g, bool xcd) {
                                  (g.epi == EPI_STORE || g.epi == EPI_QDOT || g.epi == EPI_QHEAD)),
           "gemm: LeakyReLU / SiLU / GELU run the plain and fused-loss-head paths only (kernels.hip kActRt)");
   REQUIRE(g.mode != GEMM_DX || !norm, "gemm: no DX variant with normed operands");
-  REQUIRE(g.mode != GEMM_DW || g.epi == EPI_ADAM, "gemm: DW is always fused with Adam");
-  REQUIRE(g.mode != GEMM_DW || act == ACT_NONE || (act == kDwGs && !norm && g.gscale) ||
+  REQUIRE(g.mode != GEMM_DW || g.epi == EPI_ADAM || g.epi == EPI_GSQ,
+          "gemm: DW is always fused with Adam (or is its norm pass, EPI_GSQ)");
+  REQUIRE(g.epi != EPI_GSQ || (g.mode == GEMM_DW && g.adam.gsq && g.adam.gsq_b),
+          "gemm: the norm pass is a weight gradient with partial slots for the weights and the bias");
+  // (kDwGs with normed operands: the clipped TD7 programs' scaled Adam pass; kDwNb | kDwGs has no compiled form --
+  // clipped programs run without RLE_FUSE_NBDEFER)
+  REQUIRE(g.mode != GEMM_DW || act == ACT_NONE || (act == kDwGs && g.gscale) ||
               (act == kDwNb && !norm && g.nbx.t && g.nbm.part && g.nbdot && g.R <= 1024),
           "gemm: deferred AvgL1Norm backward / gradient scale operands");
   REQUIRE(g.mode != GEMM_DW || (act == kDwGs) == (g.gscale != nullptr), "gemm: gscale is the kDwGs variant's");
@@ -157,7 +162,7 @@ void gemm_finalize(GemmArgs& g, bool xcd) {
   h.N = g.N;
   h.R = g.R;
   h.inv_tiles_n = g.inv_tiles_n;
-  h.bias_col = g.epi == EPI_ADAM ? g.adam.bias_col : 0;
+  h.bias_col = g.epi == EPI_ADAM || g.epi == EPI_GSQ ? g.adam.bias_col : 0;
   h.nseg_a = g.A.nseg;
   h.nseg_b = g.B.nseg;
   h.a0xs = g.A.seg[0].xs;
@@ -166,7 +171,7 @@ void gemm_finalize(GemmArgs& g, bool xcd) {
   h.b0xs = g.B.seg[0].xs;
   h.a0p = g.A.seg[0].p;
   h.b0p = g.B.seg[0].p;
-  h.bias = g.epi == EPI_ADAM ? nullptr : g.bias;
+  h.bias = g.epi == EPI_ADAM || g.epi == EPI_GSQ ? nullptr : g.bias;
   h.tiles = (g.hot.wide ? g.tiles_m / 4 : g.tiles_m) * g.tiles_n;
   xcd_plan(g, xcd);
 }
@@ -291,8 +296,9 @@ void GemmAudit::audit_gemm(const GemmArgs& g0) {
       jt = t - it * g.tiles_n;
     }
     const int i0 = it * 16, jt0 = jt * g.tn;
-    const int bias_col = g.epi == EPI_ADAM ? g.adam.bias_col : 0;
-    const bool bias_tile = g.epi == EPI_ADAM && jt0 >= bias_col;
+    const bool dw_epi = g.epi == EPI_ADAM || g.epi == EPI_GSQ;  // (the norm pass tiles as its Adam pass does)
+    const int bias_col = dw_epi ? g.adam.bias_col : 0;
+    const bool bias_tile = dw_epi && jt0 >= bias_col;
     bool on[4];
     for (int cb = 0; cb < NB; ++cb) on[cb] = bias_tile ? cb == 0 : jt0 + cb * 16 < g.N;
     for (int w = 0; w < 4; ++w) {
@@ -424,6 +430,12 @@ void GemmAudit::audit_gemm(const GemmArgs& g0) {
           }
           break;
         }
+        case EPI_GSQ: {  // (the norm pass: the tile's partial and nothing else)
+          const AdamArgs& ad = g.adam;
+          if (bias_tile) audit_range(ad.gsq_b, (long long)it * 4, 4, "gsq_b", g, 1);
+          else audit_range(ad.gsq, ((long long)it * (g.tiles_n - 1) + jt) * 4, 4, "gsq", g, 1);
+          break;
+        }
         default: {
           audit_mat(g.out, i0, j0, "out", g, false, false, 1);
           if (g.bias) audit_range(g.bias, (long long)j0 * 4, (long long)ncol * 4, "bias", g);
@@ -476,6 +488,7 @@ void GemmAudit::audit_gemm(const GemmArgs& g0) {
     audit_range(g.adam.bc2s, 0, 4, "adam bc2s", g);
     if (g.gscale) audit_range(g.gscale, 0, 4, "adam gscale", g);
   }
+  if (g.epi == EPI_GSQ && g.gscale) audit_range(g.gscale, 0, 4, "gsq gscale", g);
   if (g.has_pre == 2) {  // the fused loss head (kernels.hip headdx_reduce), tile rows i0 .. i0 + 15
     const HeadArgs& h = g.hd;
     const int hn = g.head_n;
@@ -756,6 +769,14 @@ void OpAccesses::op_accesses(const Op& op, std::vector<Access>& v) const {
       acc_bytes(v, a.adv, (long long)a.nvalid * 4, 1, "awac adv");
       acc_bytes(v, a.w, (long long)a.nvalid * 4, 1, "awac w");
       acc_bytes(v, a.part, (long long)((a.nvalid + 3) / 4) * 16, 1, "awac partials");
+      break;
+    }
+    case OP_CLIP: {
+      const ClipArgs& c = op.clip;
+      acc_bytes(v, c.part, (long long)c.n * 4, 0, "clip partials");
+      if (c.gin) acc_bytes(v, c.gin, 4, 0, "clip gin");
+      acc_bytes(v, c.out, 8, 1, "clip total coef");
+      acc_bytes(v, c.scale, 4, 1, "clip scale");
       break;
     }
     case OP_FOLDBIAS: {

@@ -177,6 +177,9 @@ SIGNATURES = {
     "rle_plan_default": (_int, [ctypes.POINTER(Plan)]),
     "rle_set_plan": (_int, [_vp, ctypes.POINTER(Plan)]),
     "rle_get_plan": (_int, [_vp, ctypes.POINTER(Plan)]),
+    "rle_set_grad_clip": (_int, [_vp, ctypes.c_float]),
+    "rle_get_grad_clip": (_int, [_vp, _f32p]),
+    "rle_grad_clip_stats": (_int, [_vp, _f32p]),
     "rle_bind_replay": (_int, [_vp, _vp]),
     "rle_param_numel": (_int, [_vp, _cs, _cs, _i64p]),
     "rle_get_param": (_int, [_vp, _cs, _cs, _f32p, _ll]),
@@ -399,6 +402,22 @@ class Engine:
         p = Plan()
         _check(lib().rle_get_plan(self.h, ctypes.byref(p)))
         return plan_dict(p)
+
+    def set_grad_clip(self, max_norm: float):
+        """Clip every optimizer of the step to this global L2 norm (0 or inf: off).  Before the first step."""
+        _check(lib().rle_set_grad_clip(self.h, ctypes.c_float(max_norm)))
+
+    def grad_clip(self) -> float:
+        """The clipping threshold in effect (0.0: off)."""
+        v = np.zeros(1, np.float32)
+        _check(lib().rle_get_grad_clip(self.h, _fp(v)))
+        return float(v[0])
+
+    def grad_clip_stats(self) -> dict:
+        """{optimizer: (total norm, clip coefficient)} of each optimizer's last update (NaN: none yet, or off)."""
+        v = np.zeros(6, np.float32)
+        _check(lib().rle_grad_clip_stats(self.h, _fp(v)))
+        return {k: (float(v[2 * i]), float(v[2 * i + 1])) for i, k in enumerate(("critics", "policy", "encoder"))}
 
     def close(self):
         if self.h:

@@ -34,6 +34,8 @@ class EngineAgent(Agent, Sampler):
     # (class defaults: agents pickled before these existed load without them)
     _ext: dict = {}   # rle_config_ext settings (make_config_ext), re-applied by every _new_engine
     obs_norm = None   # (mean, scale) fed to the act path by sample(), set_obs_norm
+    # global gradient-norm threshold of every optimizer of a step (rle_set_grad_clip); inf: off
+    clip_grad_norm: float = math.inf
 
     def _setup(self, env_id, *, hidden, batch_size, seed, device, make_nn, make_nn_kwargs, cfg):
         custom = None
@@ -97,7 +99,25 @@ class EngineAgent(Agent, Sampler):
         c = E.make_config(self.ALGO, self.state_dim, self.action_dim, self.hidden, batch, seed=self.seed,
                           device=self._device, **self._cfg, **self.shape, **getattr(self, "acts", {}))
         ext = getattr(self, "_ext", None)
-        return E.Engine(c, ext=E.make_config_ext(**ext) if ext else None)
+        eng = E.Engine(c, ext=E.make_config_ext(**ext) if ext else None)
+        clip = float(getattr(self, "clip_grad_norm", math.inf))
+        if clip != math.inf:  # (an agent pickled before the attribute existed, or left at inf: the unclipped step)
+            eng.set_grad_clip(clip)
+        return eng
+
+    def _set_clip(self, clip_grad_norm):
+        """The constructors' keyword, checked as rle_set_grad_clip checks it (before the engine exists)."""
+        c = float(clip_grad_norm)
+        if not c >= 0.0:
+            raise ValueError("clip_grad_norm must be >= 0 (0 or inf: no clipping)")
+        if c != math.inf:  # (inf stays the class default: nothing new in the instance dict or its pickle)
+            self.clip_grad_norm = c
+
+    def grad_clip_stats(self) -> dict:
+        """{optimizer: (total gradient norm, clip coefficient)} of the last update of each of this agent's
+        optimizers ("critics", "policy", TD7's "encoder"); NaN before an optimizer's first step, or unclipped."""
+        st = self.engine.grad_clip_stats()
+        return {k: v for k, v in st.items() if k != "encoder" or self.ALG == "td7"}
 
     def set_obs_norm(self, mean, scale=None):
         """``sample()`` feeds ``(obs - mean) / scale`` to the act path (fp32, on the host): the observation

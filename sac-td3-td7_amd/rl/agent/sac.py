@@ -13,7 +13,11 @@ class SAC(EngineAgent):
 
     Constructor arguments as the reference (sac.py:27-42) plus ``hidden``,
     ``batch_size``, ``seed`` and ``device``.  ``max_grad_norm`` is stored but, as in
-    the reference, never applied.
+    the reference, never applied (a reference script runs unchanged); the keyword-only
+    ``clip_grad_norm`` is what clips: every step, the critics' optimizer (q1 + q2) and the
+    policy's are each clipped to that global L2 norm in the device step, as
+    ``torch.nn.utils.clip_grad_norm_`` would (the temperature is never clipped);
+    ``grad_clip_stats()`` reports each optimizer's last norm and coefficient.
 
     ``offline=True`` trains from a fixed dataset with AWAC (Nair et al. 2020): the critic step is SAC's at a fixed
     temperature of 0, and the policy step maximises the advantage-weighted log-likelihood of the batch's stored
@@ -33,7 +37,10 @@ class SAC(EngineAgent):
                  tau: float = 0.005, tmp: float = -1.0, use_lap: bool = False,
                  max_grad_norm: float = float("inf"), make_nn=None, *, hidden: int = 256,
                  batch_size: int = 256, seed: int | None = None, device=None, offline: bool = False,
-                 lmbda: float = 1.0, **make_nn_kwargs) -> None:
+                 lmbda: float = 1.0, clip_grad_norm: float = float("inf"), **make_nn_kwargs) -> None:
+        # (clip_grad_norm: global-norm clipping of the critics' and the policy's optimizer steps, applied in the
+        # device step; the positional max_grad_norm stays what it is in the reference -- stored, never applied)
+        self._set_clip(clip_grad_norm)
         self.offline = bool(offline)
         self.lmbda = float(lmbda)
         if self.offline:

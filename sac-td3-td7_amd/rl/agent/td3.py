@@ -19,6 +19,10 @@ class TD3(EngineAgent):
     batch's stored action; ``Q = min(q1, q2)`` as this code base's TD3 objective), and the info dict gains two
     keys, ``train/bc`` (the mse) and ``train/lmbda`` (None on other steps).  The recipe's state normalisation is
     the replay's ``normalize_states()`` and the agent's ``set_obs_norm``.  ``offline=False`` ignores ``alpha``.
+
+    ``clip_grad_norm`` (keyword-only, default inf = off) clips the critics' optimizer (q1 + q2) every step and the
+    policy's on policy steps to that global L2 norm, as ``torch.nn.utils.clip_grad_norm_`` would; ``norm/policy``
+    stays the norm before clipping, and ``grad_clip_stats()`` reports each optimizer's last norm and coefficient.
     """
 
     ALG = "td3"
@@ -32,7 +36,9 @@ class TD3(EngineAgent):
                  critic_lr: float = 3e-4, exploration_noise: float = 0.1, target_policy_noise: float = 0.2,
                  noise_clip: float = 0.5, policy_freq: int = 2, tau: float = 0.005, use_lap: bool = False,
                  make_nn=None, *, hidden: int = 256, batch_size: int = 256, seed: int | None = None,
-                 device=None, offline: bool = False, alpha: float = 2.5, **make_nn_kwargs) -> None:
+                 device=None, offline: bool = False, alpha: float = 2.5,
+                 clip_grad_norm: float = float("inf"), **make_nn_kwargs) -> None:
+        self._set_clip(clip_grad_norm)  # (global-norm clipping of the critics' and the policy's optimizer steps)
         self.offline = bool(offline)
         self.alpha = float(alpha)
         if self.offline:  # (_ext: every engine this agent builds -- _rebuild, pickle, deepcopy, to() -- carries it)

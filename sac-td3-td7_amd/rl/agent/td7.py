@@ -20,6 +20,10 @@ class TD7(EngineAgent):
     ``lmbda * mean|Q|.detach() * mse(pi(s), a)`` (``a``: the batch's stored action), and the info dict
     two keys, ``train/bc`` (the mse) and ``train/q_abs`` (None on other steps).  ``offline=False``
     ignores ``lmbda``.
+
+    ``clip_grad_norm`` (keyword-only, default inf = off) clips the encoder's and the critics' (q1 + q2)
+    optimizers every step and the policy's on policy steps to that global L2 norm, as
+    ``torch.nn.utils.clip_grad_norm_`` would; ``grad_clip_stats()`` reports each one's last norm and coefficient.
     """
 
     ALG = "td7"
@@ -34,7 +38,8 @@ class TD7(EngineAgent):
                  target_policy_noise: float = 0.2, noise_clip: float = 0.5, policy_freq: int = 2,
                  use_lap: bool = False, make_nn=None, *, hidden: int = 256, batch_size: int = 256,
                  seed: int | None = None, device=None, offline: bool = False, lmbda: float = 0.1,
-                 **make_nn_kwargs) -> None:
+                 clip_grad_norm: float = float("inf"), **make_nn_kwargs) -> None:
+        self._set_clip(clip_grad_norm)  # (global-norm clipping of the encoder's, critics' and policy's optimizer steps)
         self.discount_factor = discount_factor
         self.target_update_rate = target_update_rate
         self.target_policy_noise = target_policy_noise
