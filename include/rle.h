@@ -284,6 +284,20 @@ int rle_get_grad_clip(rle_engine* e, float* max_norm);  /* (0: off) */
 /* {total, coef} of the last update of each optimizer: [0] critics, [1] policy, [2] TD7 encoder (NaN for an
  * optimizer that has not stepped or when clipping is off).  Syncs. */
 int rle_grad_clip_stats(rle_engine* e, float* out6);
+/* Parameter-free LayerNorm (torch.nn.LayerNorm(width, elementwise_affine=False), eps 1e-5) after every hidden
+ * Linear of q1, q2 and their targets, before the activation; the H -> 1 output layer and the actor are unchanged.
+ * It runs in every pass of the critics: the target, online and policy passes of the step, AWAC's forward-only
+ * passes and rle_eval(RLE_EVAL_Q).  Per row, in fp32, over the layer's `width` columns: mu = sum z / width,
+ * var = sum (z - mu)^2 / width (biased, two passes), u = (z - mu) / sqrt(var + 1e-5), h = act(u).  No parameter:
+ * the parameter arena, the packed state, the state_dict names and rle_copy_state / rle_copy_nets / rle_state_*
+ * are unchanged and work between engines whose setting differs.
+ * critic: 0 off (default: the programs and the kernel instance of today, op for op), 1 on (the programs then run
+ * on a kernel instance of their own, the critic heads stand-alone; composes with every activation, both offline
+ * modes and rle_set_grad_clip).  TD3 / SAC only (TD7: RLE_EINVAL).  Before the engine's first step (RLE_ESTATE
+ * after it); forward programs captured earlier (rle_eval) are dropped and rebuilt.
+ * Not run: an affine LayerNorm, another eps, LayerNorm in the actor, RMSNorm / BatchNorm. */
+int rle_set_layer_norm(rle_engine* e, int critic);
+int rle_get_layer_norm(rle_engine* e, int* critic);
 /* Bind the replay the step samples from (the replay_buffer arg of train_ops). */
 int rle_bind_replay(rle_engine* e, rle_replay* r);
 /* Parameter import/export in the reference's state_dict layout (Agent.load_state_dict,

@@ -323,6 +323,9 @@ struct Engine {
   // the rle_level instance this engine's programs run on (ops.h KernelSet): the agent's own set, or the
   // extended instance when the plan asks for its opt-in paths
   int kernel_set() const {
+    // (LayerNorm critics: OP_LN / OP_LN_BWD are KS_LN's alone; it holds KS_CLIP's code, so they compose with
+    // clipping, every activation and both offline modes)
+    if (ln_on()) return KS_LN;
     // (gradient clipping: EPI_GSQ, the scaled Adam pass over normed operands and OP_CLIP are KS_CLIP's alone; it
     // holds KS_ACT's code, so every activation and offline mode clips)
     if (clip_on()) return KS_CLIP;
@@ -343,6 +346,10 @@ struct Engine {
   float* clip_buf = nullptr;
   int clip_id[3] = {-1, -1, -1};
   bool clip_on() const { return clip_max > 0.f; }
+  // LayerNorm critics (rle_set_layer_norm): parameter-free LayerNorm, eps 1e-5, after every hidden Linear of q1, q2
+  // and their targets, before the activation (TD3 / SAC)
+  bool ln_critic = false;
+  bool ln_on() const { return ln_critic; }
   void resolve_plan() {
     if (plan.steps_per_graph < 0) plan.steps_per_graph = algo == RLE_TD3 ? 16 : algo == RLE_SAC ? 8 : 6;
     // (SAC's target critics' raw-head pre-GEMM consumers: 32 measured +1.0% over 64, 2 pairs)
@@ -1053,6 +1060,9 @@ struct Engine {
   bool fused(unsigned bit) const {
     // (clipped programs: the AvgL1Norm backward stays an op of its own, so kDwNb needs no norm-pass and no scaled form)
     if (clip_on() && (bit & RLE_FUSE_NBDEFER)) return false;
+    // (LayerNorm critics: the rule of the non-default activations, wholesale -- no in-tile recomputation of a
+    // layer, no q-dot partials, no head inside an input gradient; the norm sits between a Linear and its consumers)
+    if (ln_on() && (bit & (kActFusions | kCriticActFusions))) return false;
     if (!acts_default && (bit & kActFusions)) return false;
     if (!acts_default && actC == ACT_NONE && (bit & kCriticActFusions)) return false;
     return (bit & RLE_FUSE_OPT_IN) ? (plan.fuse_on & bit) != 0 : !(plan.fuse_off & bit);
@@ -1279,6 +1289,16 @@ struct Engine {
     // group, which clip_close() emits behind the group's OP_CLIP
     ClipGroup* clip = nullptr;
     DwOpt& clip_in(ClipGroup* g) { return clip = g, *this; }
+  };
+  // The row-norm ops of the LayerNorm critics (ln_fwd / ln_bwd).  Default: a forward-only layer -- the output in its
+  // N image alone, nothing kept for a backward.
+  struct LnOpt {
+    bool t = false;          // the output's T image too (a weight gradient reads it)
+    View* u = nullptr;       // ln_fwd: keep the normalised rows (N image) and their rstd ([rows]) for ln_bwd
+    View* rstd = nullptr;
+    LnOpt() {}
+    LnOpt& keep_t(bool on) { return t = on, *this; }
+    LnOpt& keep_bwd(View* u_out, View* rstd_out) { return u = u_out, rstd = rstd_out, *this; }
   };
   struct NormBwdOpt {
     bool n = true, t = true;  // output images, as DxOpt's
@@ -1774,6 +1794,59 @@ struct Engine {
     a.norm = x.nref();
     op.wg_count = cdiv(gv.rows, 4);
     pg.add(op, {gv.id, x.id, x.norm_id}, {out.id});
+    return out;
+  }
+
+  // LayerNorm critics (ops.h LnArgs).  ln_fwd: h = act(LayerNorm(z)) of a hidden layer of `width` columns from its
+  // Linear's output z (a fwd() with the identity epilogue); rows at or past nvalid come out zero.  ln_bwd: dz of
+  // that Linear's output from dh, the gradient of h (an input gradient with no derivative mask, or the standalone
+  // head's), and what ln_fwd kept.
+  View ln_fwd(Prog& pg, const View& z, int width, int nvalid, int act, const LnOpt& o = {}) {
+    REQUIRE(z.m.n && z.rows % 16 == 0 && width >= 4 && width <= 512 && width % 4 == 0 && z.cols == r16(width) &&
+                nvalid >= 0 && nvalid <= z.rows && !o.u == !o.rstd,
+            "ln_fwd: operand layout (widths 4 .. 512 in steps of 4)");
+    Op op{};
+    op.kind = OP_LN;
+    LnArgs& a = op.ln;
+    View out = buf(z.rows, width, true, o.t);
+    std::vector<int> wr{out.id};
+    a.x = z.m;
+    a.y = out.m;
+    if (o.u) {
+      *o.u = buf(z.rows, width, true, false);
+      *o.rstd = vec(z.rows);
+      a.u = o.u->m;
+      a.rstd = o.rstd->p;
+      wr.insert(wr.end(), {o.u->id, o.rstd->id});
+    }
+    a.rows = z.rows;
+    a.nvalid = nvalid;
+    a.width = width;
+    a.act = act;
+    op.wg_count = cdiv(z.rows, 4);  // (one row per wave)
+    pg.add(op, {z.id}, wr);
+    return out;
+  }
+  View ln_bwd(Prog& pg, const View& dh, const View& u, const View& rstd, int width, int nvalid, int act,
+              const LnOpt& o = {}) {
+    REQUIRE(dh.m.n && u.m.n && rstd.p && dh.rows % 16 == 0 && u.rows == dh.rows && rstd.rows == dh.rows &&
+                width >= 4 && width <= 512 && width % 4 == 0 && dh.cols == r16(width) && u.cols == dh.cols &&
+                nvalid >= 0 && nvalid <= dh.rows,
+            "ln_bwd: operand layout");
+    Op op{};
+    op.kind = OP_LN_BWD;
+    LnArgs& a = op.ln;
+    View out = buf(dh.rows, width, true, o.t);
+    a.x = dh.m;
+    a.y = out.m;
+    a.u = u.m;
+    a.rstd = rstd.p;
+    a.rows = dh.rows;
+    a.nvalid = nvalid;
+    a.width = width;
+    a.act = act;
+    op.wg_count = cdiv(dh.rows, 4);
+    pg.add(op, {dh.id, u.id, rstd.id}, {out.id});
     return out;
   }
 
@@ -2756,6 +2829,28 @@ struct Engine {
                       .q_dot(last && qd ? &Q.layers[D] : nullptr).keep_t(out_t && (!last || last_t)));
     }
   }
+  // The stack with LayerNorm critics (rle_set_layer_norm): per hidden layer the Linear with the identity epilogue
+  // (N image only: the norm is its one reader), then OP_LN -- one more level per layer.  M rows, the first nvalid
+  // of them real.  us / rs: the normalised rows and rstd of every layer, for the backward (null: forward only).
+  void mlp_critic_fwd_ln(Prog& pg, Net& Q, const View& sv, const View& av, int M, int nvalid, std::vector<View>& hs,
+                         bool out_t, bool last_t = true, std::vector<View>* us = nullptr,
+                         std::vector<View>* rs = nullptr) {
+    const int D = (int)Q.layers.size() - 1;
+    hs.assign(D, View{});
+    if (us) us->assign(D, View{}), rs->assign(D, View{});
+    for (int i = 0; i < D; ++i) {
+      const View z = i ? fwd(pg, Q.layers[i], {{hs[i - 1]}}, M, ACT_NONE, FwdOpt().no_t())
+                       : fwd(pg, Q.layers[0], {{sv}, {av}}, M, ACT_NONE, FwdOpt().no_t());
+      hs[i] = ln_fwd(pg, z, Q.layers[i].out, nvalid, actC,
+                     LnOpt().keep_t(out_t && (i < D - 1 || last_t)).keep_bwd(us ? &(*us)[i] : nullptr, us ? &(*rs)[i] : nullptr));
+    }
+  }
+  // rle_eval(RLE_EVAL_Q) on a LayerNorm critic: the stack above and the H -> 1 layer
+  View mlp_critic_eval_ln(Prog& pg, Net& Q, const View& sv, const View& av, int M, int nvalid) {
+    std::vector<View> hs;
+    mlp_critic_fwd_ln(pg, Q, sv, av, M, nvalid, hs, /*out_t*/ false);
+    return fwd(pg, Q.layers.back(), {{hs.back()}}, M, ACT_NONE);
+  }
   // TD3 / SAC: the critic loss head and the actor objective's head fused into the DX of each
   // critic's last hidden layer (GemmArgs::has_pre 2; one level fewer on the critic chain and on
   // the policy chain).  without RLE_FUSE_HEADDX: the standalone heads (tests, A/B).
@@ -2870,6 +2965,7 @@ struct Engine {
   // y per row, then the loss), the priority update and the next step's batch.  The backward reads:
   struct MlpCritics {
     std::vector<View> c[2], cz[2];  // the hidden layers' outputs and (ELU critics) pre-activations
+    std::vector<View> crs[2];       // LayerNorm critics: cz holds the normalised rows u, crs their rstd
     View dz1[2], dq[2];             // the head's gradients: dZ of the last hidden layer, dq
     bool hdx = false;               // the head ran inside the DX of each critic's last hidden layer, ...
     View d0f[2];                    // ... which gave dZ of the layer before
@@ -2883,18 +2979,24 @@ struct Engine {
     MlpCritics o;
     std::vector<View> th[2];
     o.hdx = mlp_headdx();
+    const bool ln = ln_on();
+    REQUIRE(!ln || !o.hdx, "LayerNorm critics: the heads run stand-alone");
     for (int n = 0; n < 2; ++n)  // (forward only)
-      mlp_critic_fwd(pg, *tq[n], sb.s2, ac.a_next, th[n], /*out_t*/ false, ac.tpre(), true, o.hdx);
+      if (ln) mlp_critic_fwd_ln(pg, *tq[n], sb.s2, ac.a_next, B, Bv, th[n], /*out_t*/ false);
+      else mlp_critic_fwd(pg, *tq[n], sb.s2, ac.a_next, th[n], /*out_t*/ false, ac.tpre(), true, o.hdx);
     for (int n = 0; n < 2; ++n)
-      mlp_critic_fwd(pg, *q[n], sb.s, act_in, o.c[n], /*out_t*/ true, nullptr, true, o.hdx, &o.cz[n]);
-    // (the loss head's derivative rows: ELU' reads the pre-activation; ReLU' / identity the output)
-    const bool cze = act_zsaved(actC);
+      if (ln) mlp_critic_fwd_ln(pg, *q[n], sb.s, act_in, B, Bv, o.c[n], /*out_t*/ true, true, &o.cz[n], &o.crs[n]);
+      else mlp_critic_fwd(pg, *q[n], sb.s, act_in, o.c[n], /*out_t*/ true, nullptr, true, o.hdx, &o.cz[n]);
+    // (the loss head's derivative rows: ELU' reads the pre-activation; ReLU' / identity the output.  LayerNorm
+    // critics: the head leaves dh = dq w, no derivative -- OP_LN_BWD takes act' from u)
+    const bool cze = act_zsaved(actC) && !ln;
     // (the last hidden layers and the heads' layers)
     const View c1[2] = {o.c[0][D - 1], o.c[1][D - 1]}, th1[2] = {th[0][D - 1], th[1][D - 1]};
     const View cz1[2] = {o.cz[0][D - 1], o.cz[1][D - 1]};
     const Layer *qo[2] = {&q[0]->layers[D], &q[1]->layers[D]}, *tqo[2] = {&tq[0]->layers[D], &tq[1]->layers[D]};
     LossHead lh = loss_head(sb, HEAD_MLP_LOSS, HEAD_MLP_TARGET, c1, cze ? cz1 : c1, th1, qo, tqo, o.hdx, lap);
     HeadArgs& h = lh.op.head;
+    if (ln) h.dact = ACT_NONE;
     if (sac) set_head_sac(h, ac.logpi, B, lh.rd);  // (the next-state rows)
     if (cze) lh.rd.insert(lh.rd.end(), {cz1[0].id, cz1[1].id});
     for (int n = 0; n < 2; ++n) o.dz1[n] = lh.dz[n], o.dq[n] = lh.dq[n];
@@ -2924,6 +3026,18 @@ struct Engine {
     for (int n = 0; n < 2; ++n) {
       Net& Q = net(n ? "q2" : "q1");
       dw(pg, Q.layers[D], cr.dq[n], {cr.c[n][D - 1]}, B, CNT_ADAM_Q, cfg.critic_lr, qo);
+      if (ln_on()) {
+        // dh of hidden layer i (the head's, then an input gradient with no mask) -> OP_LN_BWD -> dZ of its Linear,
+        // which the layer's weight gradient (T image) and the next input gradient (N image) read
+        View dh = cr.dz1[n];
+        for (int i = D - 1; i >= 0; --i) {
+          const View dzi = ln_bwd(pg, dh, cr.cz[n][i], cr.crs[n][i], Q.layers[i].out, Bv, actC, LnOpt().keep_t(true));
+          if (i) dh = dx(pg, {{dzi, &Q.layers[i], 0}}, HS[i - 1], B, DxOpt().no_t());
+          if (i) dw(pg, Q.layers[i], dzi, {cr.c[n][i - 1]}, B, CNT_ADAM_Q, cfg.critic_lr, qo);
+          else dw(pg, Q.layers[0], dzi, {sb.s, act_in}, B, CNT_ADAM_Q, cfg.critic_lr, qo);
+        }
+        continue;
+      }
       View d = cr.dz1[n];  // dZ of hidden layer i, from i = D - 1 down
       for (int i = D - 1; i >= 1; --i) {
         const View dp = cr.hdx && i == D - 1 ? cr.d0f[n]
@@ -2943,10 +3057,14 @@ struct Engine {
     Net* q[2] = {&net("q1"), &net("q2")};
     const Layer* qo[2] = {&q[0]->layers[D], &q[1]->layers[D]};
     const View &s = sb.s, &a_pi = ac.a_pi, &raw = ac.raw;
-    const bool hdx = mlp_headdx(), cze = act_zsaved(actC);
-    std::vector<View> pc[2], pcz[2];
+    const bool ln = ln_on();
+    const bool hdx = mlp_headdx(), cze = act_zsaved(actC) && !ln;
+    REQUIRE(!ln || !hdx, "LayerNorm critics: the heads run stand-alone");
+    std::vector<View> pc[2], pcz[2], prs[2];  // (LayerNorm critics: pcz holds u, prs rstd)
     for (int n = 0; n < 2; ++n)
-      mlp_critic_fwd(pg, *q[n], s, a_pi, pc[n], /*out_t*/ true, nullptr, /*last_t*/ false, hdx, &pcz[n]);
+      // (LayerNorm critics: no T image at all -- no weight gradient here, and no input gradient reads a mask)
+      if (ln) mlp_critic_fwd_ln(pg, *q[n], s, a_pi, B, Bv, pc[n], /*out_t*/ false, false, &pcz[n], &prs[n]);
+      else mlp_critic_fwd(pg, *q[n], s, a_pi, pc[n], /*out_t*/ true, nullptr, /*last_t*/ false, hdx, &pcz[n]);
     const View p1[2] = {pc[0][D - 1], pc[1][D - 1]};
     // (no weight gradient of the critics in the policy pass: the gradients keep N images only)
     const DxOpt po = DxOpt().no_t();
@@ -2959,7 +3077,7 @@ struct Engine {
     Op op = head_op(HEAD_MLP_POLICY, Bv);
     HeadArgs& h = op.head;
     set_head_twin(h, p1[0], p1[1], *qo[0], *qo[1]);
-    h.dact = actC;
+    h.dact = ln ? ACT_NONE : actC;  // (LayerNorm critics: dzp1 is dh = dq w; OP_LN_BWD takes act' from u)
     h.loss_part = sb.ploss.p;
     std::vector<int> rd{p1[0].id, p1[1].id, qo[0]->res, qo[1]->res};
     if (!hdx) {
@@ -2974,7 +3092,7 @@ struct Engine {
     sb.ploss.id = next_id++;
     if (!hdx) pg.add(op, rd, {dzp1[0].id, dzp1[1].id, sb.ploss.id});
     View dzp0[2];
-    for (int n = 0; n < 2; ++n) {
+    for (int n = 0; n < 2 && !ln; ++n) {
       HeadUse hu{h, n, rd, {}};
       if (n == 0) hu.wr.push_back(sb.ploss.id);
       // (the fused head forms dZ = dq w act'(segment 0), as the loss head's)
@@ -2993,8 +3111,16 @@ struct Engine {
       add_bc(pg, sb, 0, 1.f, &a_pi);
       add_bc(pg, sb, hdx ? 3 : 2, bc_alpha, p1, qo);
     }
+    // (LayerNorm critics: OP_LN_BWD, then the plain input gradient, per hidden layer down to dZ of the first)
+    for (int n = 0; n < 2 && ln; ++n) {
+      View dh = dzp1[n];
+      for (int i = D - 1; i >= 0; --i) {
+        dzp0[n] = ln_bwd(pg, dh, pcz[n][i], prs[n][i], q[n]->layers[i].out, Bv, actC);
+        if (i) dh = dx(pg, {{dzp0[n], &q[n]->layers[i], 0}}, HS[i - 1], B, po);
+      }
+    }
     // (deeper critics: on down to the first hidden layer; no weight gradient reads these)
-    for (int i = D - 2; i >= 1; --i)
+    for (int i = D - 2; i >= 1 && !ln; --i)
       for (int n = 0; n < 2; ++n)
         dzp0[n] = dx(pg, {{dzp0[n], &q[n]->layers[i], 0}}, HS[i - 1], B, actC,
                      dsrc_of(actC, pc[n][i - 1], pcz[n][i - 1]), po);
@@ -3054,8 +3180,13 @@ struct Engine {
     std::vector<int> rd{ac.raw.id, act_in.id, ac.logpi.id};
     for (int n = 0; n < 2; ++n) {
       std::vector<View> hd, hv;
-      mlp_critic_fwd(pg, *q[n], sb.s, act_in, hd, /*out_t*/ false);
-      mlp_critic_fwd(pg, *q[n], sb.s, ac.a_pi, hv, /*out_t*/ false);
+      if (ln_on()) {
+        mlp_critic_fwd_ln(pg, *q[n], sb.s, act_in, B, Bv, hd, /*out_t*/ false);
+        mlp_critic_fwd_ln(pg, *q[n], sb.s, ac.a_pi, B, Bv, hv, /*out_t*/ false);
+      } else {
+        mlp_critic_fwd(pg, *q[n], sb.s, act_in, hd, /*out_t*/ false);
+        mlp_critic_fwd(pg, *q[n], sb.s, ac.a_pi, hv, /*out_t*/ false);
+      }
       const View qd = fwd(pg, q[n]->layers[D], {{hd[D - 1]}}, B, ACT_NONE, FwdOpt().no_t());
       const View qv = fwd(pg, q[n]->layers[D], {{hv[D - 1]}}, B, ACT_NONE, FwdOpt().no_t());
       a.qd[n] = qd.m;
@@ -3280,7 +3411,11 @@ struct Engine {
       for (size_t k = 0; k < levels[l].size(); ++k) {
         const Op& op = levels[l][k];
         G.desc += std::string(" ") + (pg.crit_lv[l][k] ? "*" : "") +
-                  (op.kind == OP_AWAC ? "awac" : op.kind == OP_CLIP ? "clip" : kname[op.kind]);
+                  (op.kind == OP_AWAC   ? "awac"
+                   : op.kind == OP_CLIP ? "clip"
+                   : op.kind == OP_LN   ? "ln"
+                   : op.kind == OP_LN_BWD ? "ln-bwd"
+                                          : kname[op.kind]);
         if (op.kind == OP_GEMM) {
           static const char* kepi[] = {"st", "adam", "mse", "qhead", "nbdot", "act", "qdot", "sacbwd", "sacfwd", "gsq"};
           static_assert(sizeof(kepi) / sizeof(kepi[0]) == EPI_GSQ + 1, "every epilogue has a name");
@@ -4489,6 +4624,39 @@ int rle_set_grad_clip(rle_engine* h, float max_norm) {
   });
 }
 
+int rle_set_layer_norm(rle_engine* h, int critic) {
+  return guard([&] {
+    REQUIRE(h, "set_layer_norm: null");
+    REQUIRE(critic == 0 || critic == 1, "set_layer_norm: critic is 0 (off) or 1 (on)");
+    Engine& e = drained(h);
+    REQUIRE(e.algo != RLE_TD7 || !critic,
+            "set_layer_norm: TD3 / SAC only (TD7's SALE critics already carry AvgL1Norm)");
+    if (e.built)
+      throw Error{RLE_ESTATE, "set_layer_norm: the engine has already built its step programs (set it before the "
+                              "first step)"};
+    if (e.ln_critic == (critic != 0)) return;
+    e.ln_critic = critic != 0;
+    // (forward programs captured under the other setting: dropped, rle_eval rebuilds them)
+    HIPCHK(hipSetDevice(e.cfg.device));
+    for (auto it = e.eval_graphs.begin(); it != e.eval_graphs.end();) {
+      if (it->first.rfind("rsample|", 0) == 0) {  // (rle_sac_rsample's: no critic in it)
+        ++it;
+        continue;
+      }
+      if (it->second.G.x) (void)hipGraphExecDestroy(it->second.G.x);
+      if (it->second.G.g) (void)hipGraphDestroy(it->second.G.g);
+      it = e.eval_graphs.erase(it);
+    }
+  });
+}
+
+int rle_get_layer_norm(rle_engine* h, int* critic) {
+  return guard([&] {
+    REQUIRE(h && critic, "get_layer_norm: null");
+    *critic = h->e->ln_critic ? 1 : 0;
+  });
+}
+
 int rle_get_grad_clip(rle_engine* h, float* max_norm) {
   return guard([&] {
     REQUIRE(h && max_norm, "get_grad_clip: null");
@@ -5191,7 +5359,8 @@ int rle_eval(rle_engine* h, int what, const char* net, const char* enc, const fl
           eg.out = e.fwd(pg, N.layers[3], {{c2}}, M, rle::ACT_NONE);
         } else {  // MLPCritic.estimate_q_value (mlp.py:98-101)
           REQUIRE(N.kind == "mlp_critic", "eval: Q needs a critic net");
-          eg.out = e.mlp_fwd(pg, N, {{eg.in0}, {eg.in1}}, M, rle::ACT_NONE, e.actC);
+          eg.out = e.ln_on() ? e.mlp_critic_eval_ln(pg, N, eg.in0, eg.in1, M, n)
+                             : e.mlp_fwd(pg, N, {{eg.in0}, {eg.in1}}, M, rle::ACT_NONE, e.actC);
         }
         eg.width = 1;
       } else {

@@ -2362,6 +2362,68 @@ __device__ __forceinline__ void op_normbwd(const CAS NormBwdArgs& a, int t) {
   if (in1) mat_str4(a.dx, row, c1, f(g1, x1));
 }
 
+// ---------------------------------------------------------------- LayerNorm critics (ops.h LnArgs; KS_LN alone)
+
+// One row per wave (4 per workgroup), lane l holding columns 4l..4l+3 (+256 in the second pass, width > 256) as
+// float4s of the N images, as op_normbwd.  in*: the lane's float4 holds valid columns (width is a multiple of 4, so
+// whole float4s); st*: it lies inside the 16-padded width and is stored -- as zero where it is not valid.
+// BWD false: OP_LN, h = act((z - mu) rstd).  BWD true: OP_LN_BWD, dz from dh, u and rstd.
+template <bool BWD>
+__device__ __forceinline__ void op_ln(const CAS LnArgs& a, int t) {
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int row = t * 4 + wave;
+  if (row >= a.rows) return;
+  const int wp = (a.width + 15) & ~15;
+  const int c0 = 4 * lane, c1 = c0 + 256;
+  const bool valid = row < a.nvalid;
+  const bool in0 = valid && c0 < a.width, in1 = valid && c1 < a.width;
+  const bool st0 = c0 < wp, st1 = c1 < wp;
+  const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  // a lane's part of a row sum, (x + y) + (z + w) of the first float4 and then of the second; 0 outside the width
+  auto lsum = [&](float4 p, float4 q) {
+    float s = in0 ? (p.x + p.y) + (p.z + p.w) : 0.f;
+    if (in1) s += (q.x + q.y) + (q.z + q.w);
+    return s;
+  };
+  auto mul = [](float4 p, float4 q) { return make_float4(p.x * q.x, p.y * q.y, p.z * q.z, p.w * q.w); };
+  const float4 x0 = in0 ? mat_ldr4(a.x, row, c0) : zero, x1 = in1 ? mat_ldr4(a.x, row, c1) : zero;
+  if constexpr (!BWD) {
+    const float mu = wave_sum(lsum(x0, x1)) / (float)a.width;
+    auto ctr = [&](float4 p) { return make_float4(p.x - mu, p.y - mu, p.z - mu, p.w - mu); };
+    const float4 d0 = ctr(x0), d1 = ctr(x1);
+    const float var = wave_sum(lsum(mul(d0, d0), mul(d1, d1))) / (float)a.width;
+    const float rstd = 1.f / sqrtf(var + 1e-5f);
+    auto scl = [&](float4 p) { return make_float4(p.x * rstd, p.y * rstd, p.z * rstd, p.w * rstd); };
+    auto actv = [&](float4 p) {
+      return make_float4(act_fwd(a.act, p.x), act_fwd(a.act, p.y), act_fwd(a.act, p.z), act_fwd(a.act, p.w));
+    };
+    const float4 u0 = in0 ? scl(d0) : zero, u1 = in1 ? scl(d1) : zero;
+    if (st0) mat_str4(a.y, row, c0, in0 ? actv(u0) : zero);
+    if (st1) mat_str4(a.y, row, c1, in1 ? actv(u1) : zero);
+    if (a.u.n) {
+      if (st0) mat_str4(a.u, row, c0, u0);
+      if (st1) mat_str4(a.u, row, c1, u1);
+    }
+    if (a.rstd && lane == 0) GW(a.rstd)[row] = valid ? rstd : 0.f;
+  } else {
+    const float4 u0 = in0 ? mat_ldr4(a.u, row, c0) : zero, u1 = in1 ? mat_ldr4(a.u, row, c1) : zero;
+    const float rstd = valid ? G(a.rstd)[row] : 0.f;
+    auto dact = [&](float4 g, float4 u) {  // du = dh act'(u)
+      return make_float4(g.x * act_bwd(a.act, u.x), g.y * act_bwd(a.act, u.y), g.z * act_bwd(a.act, u.z),
+                         g.w * act_bwd(a.act, u.w));
+    };
+    const float4 g0 = in0 ? dact(x0, u0) : zero, g1 = in1 ? dact(x1, u1) : zero;
+    const float m1 = wave_sum(lsum(g0, g1)) / (float)a.width;
+    const float m2 = wave_sum(lsum(mul(g0, u0), mul(g1, u1))) / (float)a.width;
+    auto dz = [&](float4 g, float4 u) {
+      return make_float4(rstd * ((g.x - m1) - u.x * m2), rstd * ((g.y - m1) - u.y * m2), rstd * ((g.z - m1) - u.z * m2),
+                         rstd * ((g.w - m1) - u.w * m2));
+    };
+    if (st0) mat_str4(a.y, row, c0, in0 ? dz(g0, u0) : zero);
+    if (st1) mat_str4(a.y, row, c1, in1 ? dz(g1, u1) : zero);
+  }
+}
+
 // ---------------------------------------------------------------- critic heads
 
 
@@ -3505,7 +3567,12 @@ __global__ __launch_bounds__(kThreads, RLE_WAVES) void rle_level(unsigned e0, un
     // (OP_AWAC, offline SAC: the extended instance's alone)
     RLE_OP(0, if (ks_family(KS) != KS_MLP && vid == (OP_BC >> 4)) op_bc<ks_family(KS) == KS_EXT>(op.bc, t, smem);
            else if (ks_family(KS) == KS_EXT && vid == (OP_AWAC >> 4)) op_awac(op.awac, t, smem);
-           else if (KS == KS_CLIP && vid == (OP_CLIP >> 4)) op_clip(op.clip, smem))
+           else if (ks_clip(KS) && vid == (OP_CLIP >> 4)) op_clip(op.clip, smem);
+           // (OP_LN / OP_LN_BWD, LayerNorm critics: the KS_LN instance's alone)
+           else if constexpr (KS == KS_LN) {
+             if (vid == (OP_LN >> 4)) op_ln<false>(op.ln, t);
+             else if (vid == (OP_LN_BWD >> 4)) op_ln<true>(op.ln, t);
+           })
 #undef RLE_OP
     default: break;
   }
@@ -3514,8 +3581,8 @@ __global__ __launch_bounds__(kThreads, RLE_WAVES) void rle_level(unsigned e0, un
 
 // clip_level.hip compiles this file up to here (RLE_CLIP_TU) for the KS_CLIP instance alone: a code object of its
 // own, so this translation unit's -- every other instance and the stand-alone kernels below -- is the one it was
-// before clipped programs existed, down to the kernels' addresses.
-#ifndef RLE_CLIP_TU
+// before clipped programs existed, down to the kernels' addresses.  ln_level.hip (RLE_LN_TU) does the same for KS_LN.
+#if !defined(RLE_CLIP_TU) && !defined(RLE_LN_TU)
 
 // ---------------------------------------------------------------- B = 1 act chain (ops.h ActChainArgs)
 // Row block rb of layer L in registers: column block cb = wave + 4 i of the [16][K] strip, lane l
@@ -4000,9 +4067,11 @@ int trace_stride() { return kTraceStride; }
   X(KS_EXT, "_ZN3rle9rle_levelILb0ELi2EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd")  \
   X(KS_TD7W, "_ZN3rle9rle_levelILb0ELi3EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd") \
   X(KS_ACT, "_ZN3rle9rle_levelILb0ELi4EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd")
-// (KS_CLIP: the last KernelSet, instantiated in clip_level.hip)
+// (KS_CLIP, KS_LN: the last two KernelSets, instantiated in clip_level.hip and ln_level.hip)
 const void* clip_level_fn(int traced);
+const void* ln_level_fn(int traced);
 constexpr const char* kClipLevelSymbol = "_ZN3rle9rle_levelILb0ELi5EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd";
+constexpr const char* kLnLevelSymbol = "_ZN3rle9rle_levelILb0ELi6EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd";
 constexpr int kLevelRows = KS_CLIP;  // instances of this translation unit
 #define RLE_ROW_KS(KS, sym) KS,
 #define RLE_ROW_FN(KS, sym) (const void*)rle_level<false, KS>,
@@ -4019,9 +4088,12 @@ constexpr bool level_rows_follow_enum() {
     if (kLevelRowKs[i] != i) return false;
   return true;
 }
-static_assert(sizeof(kLevelRowKs) == kLevelRows * sizeof(int) && level_rows_follow_enum() && KS_CLIP + 1 == KS_COUNT,
-              "RLE_LEVEL_INSTANCES: one row per KernelSet but the last, in the enum's order");
-static const void* level_fn(int traced, int ks) { return ks == KS_CLIP ? clip_level_fn(traced) : kLevel.fn[traced][ks]; }
+static_assert(sizeof(kLevelRowKs) == kLevelRows * sizeof(int) && level_rows_follow_enum() && KS_CLIP + 2 == KS_COUNT &&
+                  KS_LN + 1 == KS_COUNT,
+              "RLE_LEVEL_INSTANCES: one row per KernelSet but the last two, in the enum's order");
+static const void* level_fn(int traced, int ks) {
+  return ks == KS_CLIP ? clip_level_fn(traced) : ks == KS_LN ? ln_level_fn(traced) : kLevel.fn[traced][ks];
+}
 #undef RLE_ROW_KS
 #undef RLE_ROW_FN
 #undef RLE_ROW_FN_TRACED
@@ -4041,7 +4113,9 @@ int level_capacity() {
   return per_cu * cus;
 }
 
-const char* level_kernel_symbol(int ks) { return ks == KS_CLIP ? kClipLevelSymbol : kLevel.symbol[ks]; }
+const char* level_kernel_symbol(int ks) {
+  return ks == KS_CLIP ? kClipLevelSymbol : ks == KS_LN ? kLnLevelSymbol : kLevel.symbol[ks];
+}
 
 // Launches the instance the packet names with the packet's own argument bytes.
 hipError_t launch_packet(const LevelLaunch& L, hipStream_t st) {
@@ -4111,12 +4185,18 @@ hipError_t launch_fill(float* state, float* next_state, float* action, float* re
   return hipGetLastError();
 }
 
-#else  // RLE_CLIP_TU
+#elif defined(RLE_CLIP_TU)
 
 const void* clip_level_fn(int traced) {
   return traced ? (const void*)rle_level<true, KS_CLIP> : (const void*)rle_level<false, KS_CLIP>;
 }
 
-#endif  // RLE_CLIP_TU
+#else  // RLE_LN_TU
+
+const void* ln_level_fn(int traced) {
+  return traced ? (const void*)rle_level<true, KS_LN> : (const void*)rle_level<false, KS_LN>;
+}
+
+#endif
 
 }  // namespace rle

@@ -36,6 +36,8 @@ enum OpKind : int {
   OP_BC = 16,           // TD7 offline: the behaviour-cloning term's scalars and action-gradient operand (BcArgs)
   OP_AWAC = 32,         // offline SAC: the advantage-weighted policy step's row-wise op (AwacArgs; the extended instance)
   OP_CLIP = 48,         // gradient clipping: an optimizer's global norm and clip coefficient (ClipArgs; KS_CLIP alone)
+  OP_LN = 64,           // LayerNorm critics: a hidden layer's row norm and activation (LnArgs; KS_LN alone)
+  OP_LN_BWD = 80,       // ... and its backward, dh -> dz (LnArgs; KS_LN alone)
 };
 
 // ---------------------------------------------------------------- tensor images
@@ -238,14 +240,21 @@ constexpr bool wide_variant(int mode, int epi, int pk) {
 // KS_CLIP: KS_ACT's code plus the clipped programs' own (EPI_GSQ, the sets-4 variants, OP_CLIP), for engines with
 // rle_set_grad_clip on -- a set of its own for the same reason: every other instance is the code it was.  It is
 // instantiated in clip_level.hip, a code object of its own, so the others also stay at the addresses they had.
-enum KernelSet : int { KS_TD7 = 0, KS_MLP = 1, KS_EXT = 2, KS_TD7W = 3, KS_ACT = 4, KS_CLIP = 5, KS_COUNT = 6 };
+// KS_LN: KS_CLIP's code plus the LayerNorm critics' row ops (OP_LN, OP_LN_BWD), for engines with rle_set_layer_norm
+// on -- again a set and (ln_level.hip) a code object of its own, so every other instance is the code it was, where
+// it was.  It holds KS_CLIP's code, so LayerNorm composes with every activation, both offline modes and clipping.
+enum KernelSet : int {
+  KS_TD7 = 0, KS_MLP = 1, KS_EXT = 2, KS_TD7W = 3, KS_ACT = 4, KS_CLIP = 5, KS_LN = 6, KS_COUNT = 7
+};
+// the instances that hold the clipped programs' code (EPI_GSQ, the sets-4 variants, OP_CLIP)
+constexpr bool ks_clip(int ks) { return ks == KS_CLIP || ks == KS_LN; }
 // the agent family whose variants (RLE_GEMM_VARIANTS sets bit) and ops an instance compiles
-constexpr int ks_family(int ks) { return ks == KS_TD7W ? KS_TD7 : ks == KS_ACT || ks == KS_CLIP ? KS_EXT : ks; }
+constexpr int ks_family(int ks) { return ks == KS_TD7W ? KS_TD7 : ks == KS_ACT || ks_clip(ks) ? KS_EXT : ks; }
 // the instances that dispatch an ELU id a second time on the op's activation (kActRt: LeakyReLU / SiLU / GELU)
-constexpr bool ks_act_rt(int ks) { return ks == KS_ACT || ks == KS_CLIP; }
+constexpr bool ks_act_rt(int ks) { return ks == KS_ACT || ks_clip(ks); }
 // whether instance ks compiles a variant of RLE_GEMM_VARIANTS with this sets field
 constexpr bool variant_in_set(int sets, int ks) {
-  return (sets & 4) ? ks == KS_CLIP : ks_family(ks) == KS_EXT || ((sets >> ks_family(ks)) & 1);
+  return (sets & 4) ? ks_clip(ks) : ks_family(ks) == KS_EXT || ((sets >> ks_family(ks)) & 1);
 }
 
 enum GemmMode : int {
@@ -654,6 +663,26 @@ struct ClipArgs {
   float* scale;          // [1]
 };
 
+// LayerNorm critics (rle_set_layer_norm): torch.nn.LayerNorm(width, elementwise_affine=False), eps 1e-5, between a
+// hidden Linear and its activation, as two row-wise ops shaped like OP_NORMBWD: one row per wave (4 rows per
+// workgroup), lane l holding columns 4l..4l+3 and 256+4l.. (width > 256) as float4s of the N images.  fp32, over
+// the `width` valid columns:
+//   OP_LN      mu = sum_j z_j / width,  var = sum_j (z_j - mu)^2 / width  (two passes),  rstd = 1 / sqrt(var + 1e-5)
+//              u = (z - mu) rstd,  h = act(u)
+//   OP_LN_BWD  du = dh act'(u)  (the derivative taken from u),  dz = rstd (du - mean_j du - u mean_j (du u))
+// Each of the three row sums is the lane's own sum in a fixed order -- (x + y) + (z + w) of the first float4, then
+// plus that of the second -- followed by one wave_sum: the order depends on `width` alone.  Columns in
+// [width, 16-padded width) enter no sum and are stored as zero in h, u and dz; rows in [nvalid, rows) are stored as
+// zero, rstd 0.  A constant row has var 0 and the finite rstd 1 / sqrt(1e-5).  No parameter is read or written.
+struct LnArgs {
+  Mat x;                 // OP_LN: z, the Linear's output (N image).  OP_LN_BWD: dh (N image)
+  Mat y;                 // OP_LN: h out (N; T where a weight gradient reads it).  OP_LN_BWD: dz out (N; T likewise)
+  Mat u;                 // the normalised row: OP_LN out (N; null in a forward-only pass), OP_LN_BWD in
+  float* rstd;           // [rows]: OP_LN out (null in a forward-only pass), OP_LN_BWD in
+  int rows, nvalid;      // rows: a multiple of 16, every one stored
+  int width, act;        // width: 4 .. 512, a multiple of 4; act: the hidden activation (ACT_*), run-time
+};
+
 struct FlatArgs {   // POLYAK / COPY / MAXRED
   float* dst; const float* src; long long n;
   float tau, omt; int self_alias;     // self_alias: p <- tau*p + p*(1-tau) (TD3 quirk Q2)
@@ -689,6 +718,7 @@ struct Op {
     BcArgs bc;
     AwacArgs awac;
     ClipArgs clip;
+    LnArgs ln;
   };
 };
 // kernels.hip gemm_v touches the descriptor's 64-byte lines by fixed offsets from &gemm (its
@@ -696,7 +726,7 @@ struct Op {
 static_assert(sizeof(HeadArgs) <= sizeof(PreArgs), "GemmArgs: the fused head shares the pre-GEMM's fields");
 static_assert(sizeof(Op) % 64 == 0 && offsetof(Op, gemm) == 16, "Op layout (descriptor line touches)");
 static_assert(16 + sizeof(HeadArgs) <= 8 * 64 && 16 + sizeof(StepEndArgs) <= 8 * 64 && 16 + sizeof(SampleArgs) <= 8 * 64 &&
-                  16 + sizeof(BcArgs) <= 8 * 64 && 16 + sizeof(AwacArgs) <= 8 * 64,
+                  16 + sizeof(BcArgs) <= 8 * 64 && 16 + sizeof(AwacArgs) <= 8 * 64 && 16 + sizeof(LnArgs) <= 8 * 64,
               "rle_level touches 8 descriptor lines of a non-GEMM op");
 static_assert(offsetof(GemmArgs, A) == 0xb0 && offsetof(GemmArgs, B) == 0x1a0 && offsetof(GemmArgs, out) == 0x290 &&
                   offsetof(GemmArgs, noise) == 0x2f0 && offsetof(GemmArgs, nbx) == 0x370 &&

@@ -239,6 +239,41 @@ struct GemmAudit {
 
 void audit_gemm(const GemmArgs& g, const AuditSink& sink) { GemmAudit{sink}.audit_gemm(g); }
 
+// RLE_AUDIT=1 for a LayerNorm row op (kernels.hip op_ln): every 16 x 16 block its workgroups load or store -- rows
+// [0, rows), columns [0, 16-padded width) of each image it names -- and its rstd vector lie inside an allocation.
+static void audit_ln(const Op& op, const AllocRegistry& allocs) {
+  const LnArgs& a = op.ln;
+  const bool bwd = op.kind == OP_LN_BWD;
+  auto fail = [&](const char* what) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "audit: %s outside its allocation (%s rows %d nvalid %d width %d)", what,
+             bwd ? "ln-bwd" : "ln", a.rows, a.nvalid, a.width);
+    throw Error{RLE_EINVAL, msg};
+  };
+  auto range = [&](const void* base, long long lo, long long bytes, const char* what) {
+    uintptr_t alo, ahi;
+    const uintptr_t p = (uintptr_t)base + (uintptr_t)lo;
+    if (!base || lo < 0 || !allocs.containing(p, &alo, &ahi) || p + (uintptr_t)bytes > ahi) fail(what);
+  };
+  if (a.rows <= 0 || a.rows % 16 || a.nvalid < 0 || a.nvalid > a.rows || a.width < 4 || a.width > 512 || a.width % 4 ||
+      op.wg_count * 4 < a.rows)
+    fail("shape");
+  auto mat = [&](const Mat& m, bool need_n, const char* what) {
+    if (need_n && !m.n) fail(what);
+    if (m.cbn < (a.width + 15) / 16 && m.n) fail(what);
+    for (int r = 0; r < a.rows; r += 16)
+      for (int c = 0; c < a.width; c += 16) {
+        if (m.n) range(m.n, h_nblk(m.cbn, r, c), 1024, what);
+        if (m.t) range(m.t, h_tblk(m.rbs, r, c), 1024, what);
+      }
+  };
+  mat(a.x, true, bwd ? "ln-bwd dh" : "ln z");
+  mat(a.y, true, bwd ? "ln-bwd dz" : "ln h");
+  if (bwd || a.u.n) mat(a.u, true, "ln u");
+  if (bwd || a.rstd) range(a.rstd, 0, (long long)a.rows * 4, "ln rstd");
+  if (!bwd && !a.u.n != !a.rstd) fail("ln u / rstd (kept together)");
+}
+
 void GemmAudit::audit_range(const void* base, long long lo, long long bytes, const char* what, const GemmArgs& g,
                             int w) {
   if (bytes <= 0) return;
@@ -779,6 +814,16 @@ void OpAccesses::op_accesses(const Op& op, std::vector<Access>& v) const {
       acc_bytes(v, c.scale, 4, 1, "clip scale");
       break;
     }
+    case OP_LN:
+    case OP_LN_BWD: {  // (rows [0, rows) of every image, each row's floats scattered over its row block: whole images)
+      const LnArgs& a = op.ln;
+      const bool bwd = op.kind == OP_LN_BWD;
+      acc_mat(v, a.x, 0, bwd ? "ln-bwd dh" : "ln z");
+      acc_mat(v, a.y, 1, bwd ? "ln-bwd dz" : "ln h");
+      acc_mat(v, a.u, bwd ? 0 : 1, "ln u");
+      acc_bytes(v, a.rstd, (long long)a.rows * 4, bwd ? 0 : 1, "ln rstd");
+      break;
+    }
     case OP_FOLDBIAS: {
       const FoldBiasArgs& f = op.fb;
       acc_bytes(v, f.wn, (long long)((f.H + 15) / 16) * f.cbn * 1024, 0, "fold w");
@@ -930,6 +975,8 @@ void Prog::add_group(std::vector<Op> ops, std::vector<int> rd, std::vector<int> 
       gemm_finalize(op.gemm, opt.xcd != 0);
       check_gemm(op.gemm);
       if (opt.audit) audit_gemm(op.gemm, AuditSink{opt.allocs, nullptr});
+    } else if ((op.kind == OP_LN || op.kind == OP_LN_BWD) && opt.audit) {
+      audit_ln(op, *opt.allocs);
     }
   Item it;
   it.ops = std::move(ops);
@@ -943,6 +990,10 @@ int Prog::op_weight(const Op& op) const {
   if (op.kind == OP_GEMM)
     x = op.gemm.R * op.gemm.tn / 1024 + (op.gemm.epi == EPI_ADAM ? opt.adam_w : 0) + (op.gemm.has_pre >= 3 ? opt.pl_w : 0);
   else if (op.kind == OP_HEAD) x = opt.head_w;
+  // (a LayerNorm row op: 4 rows per workgroup, two or three float4s per lane and two wave sums -- one load round
+  // trip and two dependent reductions whatever the width, so about a narrow GEMM tile; set by that reasoning, not
+  // tuned: the ops sit alone on their levels of the critic chain, where the weight moves nothing)
+  else if (op.kind == OP_LN || op.kind == OP_LN_BWD) x = 4 + op.ln.width / 128;
   else if (op.kind == OP_SAMPLE_GATHER) x = op.sample.lap ? opt.lap_w : uniform_weight();  // (uniform: a
                                                                                      // ~6 us gather)
   else if (op.kind == OP_STEP_END && op.end.mode != 1) x = tiny_weight();  // (one workgroup, ~4 KB of straight-line

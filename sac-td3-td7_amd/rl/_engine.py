@@ -180,6 +180,8 @@ SIGNATURES = {
     "rle_set_grad_clip": (_int, [_vp, ctypes.c_float]),
     "rle_get_grad_clip": (_int, [_vp, _f32p]),
     "rle_grad_clip_stats": (_int, [_vp, _f32p]),
+    "rle_set_layer_norm": (_int, [_vp, _int]),
+    "rle_get_layer_norm": (_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
     "rle_bind_replay": (_int, [_vp, _vp]),
     "rle_param_numel": (_int, [_vp, _cs, _cs, _i64p]),
     "rle_get_param": (_int, [_vp, _cs, _cs, _f32p, _ll]),
@@ -418,6 +420,17 @@ class Engine:
         v = np.zeros(6, np.float32)
         _check(lib().rle_grad_clip_stats(self.h, _fp(v)))
         return {k: (float(v[2 * i]), float(v[2 * i + 1])) for i, k in enumerate(("critics", "policy", "encoder"))}
+
+    def set_layer_norm(self, critic: bool = True):
+        """Parameter-free LayerNorm (eps 1e-5) after every hidden Linear of the critics and their targets, before
+        the activation (TD3 / SAC).  Before the first step."""
+        _check(lib().rle_set_layer_norm(self.h, ctypes.c_int(1 if critic else 0)))
+
+    def layer_norm(self) -> bool:
+        """Whether the critics carry LayerNorm (rle_get_layer_norm)."""
+        v = ctypes.c_int(0)
+        _check(lib().rle_get_layer_norm(self.h, ctypes.byref(v)))
+        return bool(v.value)
 
     def close(self):
         if self.h:

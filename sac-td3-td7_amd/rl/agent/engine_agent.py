@@ -36,6 +36,8 @@ class EngineAgent(Agent, Sampler):
     obs_norm = None   # (mean, scale) fed to the act path by sample(), set_obs_norm
     # global gradient-norm threshold of every optimizer of a step (rle_set_grad_clip); inf: off
     clip_grad_norm: float = math.inf
+    # parameter-free LayerNorm after every hidden Linear of the critics (rle_set_layer_norm; TD3 / SAC)
+    critic_layer_norm: bool = False
 
     def _setup(self, env_id, *, hidden, batch_size, seed, device, make_nn, make_nn_kwargs, cfg):
         custom = None
@@ -45,7 +47,12 @@ class EngineAgent(Agent, Sampler):
             from rl.nn.modules import nets_from_make_nn
 
             S, A = get_state_action_dims(env_id)
-            hidden, shape, custom, acts = nets_from_make_nn(self.ALG, make_nn, S, A, make_nn_kwargs)
+            hidden, shape, custom, acts, ln = nets_from_make_nn(self.ALG, make_nn, S, A, make_nn_kwargs)
+            if self.critic_layer_norm and not ln:
+                raise ValueError("critic_layer_norm=True, but make_nn's critics carry no LayerNorm "
+                                 "(rl.nn.MLPCritic(..., layer_norm=True))")
+            if ln:  # (the hook's nets decide; False stays the class default)
+                self.critic_layer_norm = True
             make_nn_kwargs = {}
         hdim = make_nn_kwargs.pop("hdim", None)
         zs = make_nn_kwargs.pop("zs_dim", None)
@@ -103,7 +110,29 @@ class EngineAgent(Agent, Sampler):
         clip = float(getattr(self, "clip_grad_norm", math.inf))
         if clip != math.inf:  # (an agent pickled before the attribute existed, or left at inf: the unclipped step)
             eng.set_grad_clip(clip)
+        if getattr(self, "critic_layer_norm", False):  # (class default False: an older pickle loads without it)
+            eng.set_layer_norm(True)
         return eng
+
+    def _set_layer_norm(self, critic_layer_norm):
+        """The TD3 / SAC constructors' keyword (False stays the class default: nothing new in the pickle)."""
+        if critic_layer_norm:
+            self.critic_layer_norm = True
+
+    def _host_critic(self, name):
+        """A host-side rl.nn.MLPCritic with critic `name`'s current parameters (TD3 / SAC): the module the
+        reference keeps as agent.q1 / agent.q2, LayerNorm included, rebuilt from the device on each access."""
+        import torch
+
+        from rl.nn.modules import MLPCritic
+
+        fn = {"relu": "ReLU", "elu": "ELU", "identity": "Identity", "leaky_relu": "LeakyReLU", "silu": "SiLU",
+              "gelu": "GELU"}[getattr(self, "acts", {}).get("act_critic", "relu")]
+        sizes = self.shape.get("hidden_sizes", [self.hidden] * 2)
+        m = MLPCritic(self.state_dim, self.action_dim, sizes, action_fn=fn, layer_norm=self.critic_layer_norm)
+        sd = {k: torch.from_numpy(np.array(v, np.float32)) for k, v in self.state_dict()[name].items()}
+        m.load_state_dict(sd)
+        return m
 
     def _set_clip(self, clip_grad_norm):
         """The constructors' keyword, checked as rle_set_grad_clip checks it (before the engine exists)."""

@@ -24,7 +24,12 @@ class SAC(EngineAgent):
     action, ``L = -mean(w * log pi(a | s))`` with ``w = min(exp((Q(s, a) - Q(s, a_pi)) / lmbda), 100)`` detached
     (``Q = min(q1, q2)`` of the updated critics, ``a_pi`` the policy's own rsample).  No gradient passes through
     the critics.  The info dict is ``train/q_fn``, ``train/policy``, ``entropy``, ``train/adv`` (mean advantage)
-    and ``train/weight`` (mean w).  ``offline`` forces ``tmp = 0``; ``offline=False`` ignores ``lmbda``."""
+    and ``train/weight`` (mean w).  ``offline`` forces ``tmp = 0``; ``offline=False`` ignores ``lmbda``.
+
+    ``critic_layer_norm`` (keyword-only, default False) puts a parameter-free LayerNorm (``nn.LayerNorm(width,
+    elementwise_affine=False)``, eps 1e-5) after every hidden Linear of q1, q2 and their targets, before the
+    activation, in every pass of the device step (AWAC's forward-only passes included); the state_dict is
+    unchanged, and ``agent.q1`` / ``agent.q2`` give host copies (``rl.nn.MLPCritic``) that carry the norm."""
 
     ALG = "sac"
     ALGO = E.RLE_SAC
@@ -37,7 +42,10 @@ class SAC(EngineAgent):
                  tau: float = 0.005, tmp: float = -1.0, use_lap: bool = False,
                  max_grad_norm: float = float("inf"), make_nn=None, *, hidden: int = 256,
                  batch_size: int = 256, seed: int | None = None, device=None, offline: bool = False,
-                 lmbda: float = 1.0, clip_grad_norm: float = float("inf"), **make_nn_kwargs) -> None:
+                 lmbda: float = 1.0, clip_grad_norm: float = float("inf"), critic_layer_norm: bool = False,
+                 **make_nn_kwargs) -> None:
+        # (parameter-free LayerNorm after every hidden Linear of the critics and their targets, in the device step)
+        self._set_layer_norm(critic_layer_norm)
         # (clip_grad_norm: global-norm clipping of the critics' and the policy's optimizer steps, applied in the
         # device step; the positional max_grad_norm stays what it is in the reference -- stored, never applied)
         self._set_clip(clip_grad_norm)
@@ -102,6 +110,15 @@ class SAC(EngineAgent):
         """sac.py:132-152: tanh(mean) or tanh(mean + std * randn) (rsample), * scale + bias, one
         device program (rle_act_sample; engine Philox stream, or kwargs eps=[A] for parity)."""
         return self._act(state, deterministic, kwargs.get("eps"))
+
+    @property
+    def q1(self):
+        """Host copy of the first critic (rl.nn.MLPCritic, LayerNorm included), from the device parameters."""
+        return self._host_critic("q1")
+
+    @property
+    def q2(self):
+        return self._host_critic("q2")
 
     def __repr__(self) -> str:
         return "SAC"

@@ -23,6 +23,11 @@ class TD3(EngineAgent):
     ``clip_grad_norm`` (keyword-only, default inf = off) clips the critics' optimizer (q1 + q2) every step and the
     policy's on policy steps to that global L2 norm, as ``torch.nn.utils.clip_grad_norm_`` would; ``norm/policy``
     stays the norm before clipping, and ``grad_clip_stats()`` reports each optimizer's last norm and coefficient.
+
+    ``critic_layer_norm`` (keyword-only, default False) puts a parameter-free LayerNorm (``nn.LayerNorm(width,
+    elementwise_affine=False)``, eps 1e-5) after every hidden Linear of q1, q2 and their targets, before the
+    activation -- the critic of ReBRAC / RLPD -- in every pass of the device step; the state_dict is unchanged, and
+    ``agent.q1`` / ``agent.q2`` give host copies (``rl.nn.MLPCritic``) that carry the norm.
     """
 
     ALG = "td3"
@@ -37,7 +42,10 @@ class TD3(EngineAgent):
                  noise_clip: float = 0.5, policy_freq: int = 2, tau: float = 0.005, use_lap: bool = False,
                  make_nn=None, *, hidden: int = 256, batch_size: int = 256, seed: int | None = None,
                  device=None, offline: bool = False, alpha: float = 2.5,
-                 clip_grad_norm: float = float("inf"), **make_nn_kwargs) -> None:
+                 clip_grad_norm: float = float("inf"), critic_layer_norm: bool = False,
+                 **make_nn_kwargs) -> None:
+        # (parameter-free LayerNorm after every hidden Linear of the critics and their targets, in the device step)
+        self._set_layer_norm(critic_layer_norm)
         self._set_clip(clip_grad_norm)  # (global-norm clipping of the critics' and the policy's optimizer steps)
         self.offline = bool(offline)
         self.alpha = float(alpha)
@@ -66,6 +74,15 @@ class TD3(EngineAgent):
         device program (rle_act_sample).  The noise comes from the engine's Philox stream (the
         reference uses torch's global generator); kwargs eps=[A] supplies it instead (parity)."""
         return self._act(state, deterministic, kwargs.get("eps"))
+
+    @property
+    def q1(self):
+        """Host copy of the first critic (rl.nn.MLPCritic, LayerNorm included), from the device parameters."""
+        return self._host_critic("q1")
+
+    @property
+    def q2(self):
+        return self._host_critic("q2")
 
     def __repr__(self) -> str:
         return "TD3"

@@ -52,10 +52,60 @@ def _act_name(fn) -> str:
                               "Identity, LeakyReLU (slope 0.01), SiLU and GELU (exact)")
 
 
+_LN_ONLY = ("LayerNorm runs in the critics of TD3 / SAC only, as MLPCritic(layer_norm=True): "
+            "nn.LayerNorm(width, elementwise_affine=False), eps 1e-5, after every hidden Linear")
+
+
+def _no_layer_norm(kind: str, layer_norm) -> None:
+    if layer_norm:
+        raise NotImplementedError(f"{kind}(layer_norm=...): {_LN_ONLY}")
+
+
+def _check_layer_norm(layer_norm) -> bool:
+    """MLPCritic's layer_norm argument -> on / off.  True, or a description of the one form the engine runs (an
+    nn.LayerNorm instance or a dict of its keyword arguments): no affine parameters, eps 1e-5.  Anything else
+    is NotImplementedError."""
+    if layer_norm is None or layer_norm is False:
+        return False
+    if layer_norm is True:
+        return True
+    if isinstance(layer_norm, nn.LayerNorm):
+        affine, eps = layer_norm.elementwise_affine, layer_norm.eps
+    elif isinstance(layer_norm, dict):
+        extra = set(layer_norm) - {"elementwise_affine", "eps", "bias"}
+        if extra:
+            raise NotImplementedError(f"layer_norm arguments {sorted(extra)}: {_LN_ONLY}")
+        affine, eps = layer_norm.get("elementwise_affine", True), layer_norm.get("eps", 1e-5)
+    else:
+        raise NotImplementedError(f"layer_norm={layer_norm!r}: {_LN_ONLY}")
+    if affine:
+        raise NotImplementedError(f"an affine LayerNorm (elementwise_affine=True): {_LN_ONLY}")
+    if eps != 1e-5:
+        raise NotImplementedError(f"LayerNorm eps {eps}: {_LN_ONLY}")
+    return True
+
+
+class NormAct(nn.Module):
+    """One hidden block's LayerNorm and activation as a single Sequential slot, so the Linear layers of a
+    LayerNorm critic stay at indices 0, 2, 4, ... and its state_dict names are those of a plain one (the norm has
+    no parameter and no buffer).  forward: act(layer_norm(z)) -- per row mu = mean(z), var = mean((z - mu)^2),
+    u = (z - mu) / sqrt(var + 1e-5), h = act(u)."""
+
+    def __init__(self, width: int, act: nn.Module):
+        super().__init__()
+        self.norm = nn.LayerNorm(width, elementwise_affine=False)
+        self.act = act
+
+    def forward(self, z):
+        return self.act(self.norm(z))
+
+
 class SALEEncoder(_Linears):
     """sale.py:16-55: zs = AvgL1Norm(zs3(elu(zs2(elu(zs1(s)))))), zsa = zsa3(elu(zsa2(elu(zsa1([zs, a])))))."""
 
-    def __init__(self, state_dim: int, action_dim: int, zs_dim: int = 256, hdim: int = 256, activ=F.elu):
+    def __init__(self, state_dim: int, action_dim: int, zs_dim: int = 256, hdim: int = 256, activ=F.elu,
+                 layer_norm=False):
+        _no_layer_norm("SALEEncoder", layer_norm)
         super().__init__(SALE_ENCODER, {"S": state_dim, "A": action_dim, "H": hdim, "Z": zs_dim})
         self.state_dim, self.action_dim, self.zs_dim, self.hdim, self.activ = state_dim, action_dim, zs_dim, hdim, activ
 
@@ -71,7 +121,9 @@ class SALEEncoder(_Linears):
 class SALEActor(_Linears):
     """sale.py:58-83: tanh(l3(relu(l2(relu(l1([AvgL1Norm(l0(s)), zs]))))))."""
 
-    def __init__(self, state_dim: int, action_dim: int, zs_dim: int = 256, hdim: int = 256, activ=F.relu):
+    def __init__(self, state_dim: int, action_dim: int, zs_dim: int = 256, hdim: int = 256, activ=F.relu,
+                 layer_norm=False):
+        _no_layer_norm("SALEActor", layer_norm)
         super().__init__(SALE_ACTOR, {"S": state_dim, "A": action_dim, "H": hdim, "Z": zs_dim})
         self.state_dim, self.action_dim, self.zs_dim, self.hdim, self.activ = state_dim, action_dim, zs_dim, hdim, activ
 
@@ -84,7 +136,9 @@ class SALEActor(_Linears):
 class SALECritic(_Linears):
     """sale.py:86-121: q3(elu(q2(elu(q1([AvgL1Norm(q01([s, a])), zsa, zs])))))."""
 
-    def __init__(self, state_dim: int, action_dim: int, zs_dim: int = 256, hdim: int = 256, activ=F.elu):
+    def __init__(self, state_dim: int, action_dim: int, zs_dim: int = 256, hdim: int = 256, activ=F.elu,
+                 layer_norm=False):
+        _no_layer_norm("SALECritic", layer_norm)  # (its q01 output already carries AvgL1Norm)
         super().__init__(SALE_CRITIC, {"S": state_dim, "A": action_dim, "H": hdim, "Z": zs_dim})
         self.state_dim, self.action_dim, self.zs_dim, self.hdim, self.activ = state_dim, action_dim, zs_dim, hdim, activ
 
@@ -93,10 +147,11 @@ class SALECritic(_Linears):
         return self.q3(self.activ(self.q2(self.activ(self.q1(h)))))
 
 
-def _mlp(fin: int, fout: int, hidden_sizes, action_fn="ReLU", init_weight=None, init_bias=None):
+def _mlp(fin: int, fout: int, hidden_sizes, action_fn="ReLU", init_weight=None, init_bias=None, layer_norm=False):
     """make_mlp (mlp.py:10-35): Linear-act-...-Linear (indices 0, 2, 4, ...); weights by nn.init.<init_weight>
     (default xavier_normal_), biases by nn.init.<init_bias> (default zeros_).  Returns (Sequential, activation
-    name).  action_fn=None is refused: make_mlp then pops the output Linear (mlp.py:34), not an activation."""
+    name).  action_fn=None is refused: make_mlp then pops the output Linear (mlp.py:34), not an activation.
+    layer_norm: every hidden block is Linear-NormAct (LayerNorm, then the activation, in the activation's slot)."""
     if action_fn is None:
         raise NotImplementedError("make_mlp(action_fn=None) drops the output layer (mlp.py:34 pops the last Linear); "
                                   "use action_fn='Identity' for a net without activations")
@@ -110,7 +165,7 @@ def _mlp(fin: int, fout: int, hidden_sizes, action_fn="ReLU", init_weight=None, 
         lin = nn.Linear(dims[i], dims[i + 1])
         init_w(lin.weight.data)
         init_b(lin.bias.data)
-        mods += [lin, act]
+        mods += [lin, NormAct(dims[i + 1], act) if layer_norm else act]
     return nn.Sequential(*mods[:-1]), name
 
 
@@ -124,7 +179,8 @@ def _sizes(hidden_sizes):
 class MLPActor(nn.Module):
     """mlp.py:38-72: mean = mlp(s); SAC heads chunk it into (mean, log_std)."""
 
-    def __init__(self, state_dim: int, action_dim: int, hidden_sizes=256, **mlp_kwargs):
+    def __init__(self, state_dim: int, action_dim: int, hidden_sizes=256, layer_norm=False, **mlp_kwargs):
+        _no_layer_norm("MLPActor", layer_norm)
         super().__init__()
         self.state_dim, self.action_dim, self.hidden_sizes = state_dim, action_dim, _sizes(hidden_sizes)
         self.mlp, self.act = _mlp(state_dim, action_dim, self.hidden_sizes, **mlp_kwargs)
@@ -137,12 +193,15 @@ class MLPActor(nn.Module):
 
 
 class MLPCritic(nn.Module):
-    """mlp.py:75-104: q = mlp([s, a])."""
+    """mlp.py:75-104: q = mlp([s, a]).  layer_norm=True: parameter-free LayerNorm (eps 1e-5) after every hidden
+    Linear, before the activation (NormAct); the output layer is not normalised."""
 
-    def __init__(self, state_dim: int, action_dim: int, hidden_sizes=256, **mlp_kwargs):
+    def __init__(self, state_dim: int, action_dim: int, hidden_sizes=256, layer_norm=False, **mlp_kwargs):
         super().__init__()
         self.state_dim, self.action_dim, self.hidden_sizes = state_dim, action_dim, _sizes(hidden_sizes)
-        self.mlp, self.act = _mlp(state_dim + action_dim, 1, self.hidden_sizes, **mlp_kwargs)
+        self.layer_norm = _check_layer_norm(layer_norm)
+        self.mlp, self.act = _mlp(state_dim + action_dim, 1, self.hidden_sizes, layer_norm=self.layer_norm,
+                                  **mlp_kwargs)
 
     def estimate_q_value(self, state, action):
         return self.mlp(torch.cat([state, action], -1))
@@ -155,7 +214,8 @@ def nets_from_make_nn(alg: str, make_nn, state_dim: int, action_dim: int, kwargs
     one shape across the agent's nets: (hdim, zs_dim) of the SALE nets, hidden_sizes of the MLPs
     (the shape is {"zs_dim": ...} or {"hidden_sizes": [...]}, as rle_config takes them).  The
     activations are make_config's act_actor / act_critic / act_encoder (the names _act_name returns):
-    the SALE nets' `activ`, make_mlp's action_fn; the two critics must agree."""
+    the SALE nets' `activ`, make_mlp's action_fn; the two critics must agree.  A fifth value tells whether the
+    critics carry LayerNorm (MLPCritic layer_norm; both critics must agree)."""
     import numpy as np
 
     kw = dict(kwargs)
@@ -170,6 +230,7 @@ def nets_from_make_nn(alg: str, make_nn, state_dim: int, action_dim: int, kwargs
     widths = set()
     nets = {}
     acts = {}
+    lns = set()
     for name, kind, m in zip(names, kinds, out):
         if type(m) is not kind:
             raise NotImplementedError(f"make_nn returned {type(m).__name__} for {name}; the engine builds "
@@ -178,6 +239,8 @@ def nets_from_make_nn(alg: str, make_nn, state_dim: int, action_dim: int, kwargs
         act = _act_name(m.activ) if isinstance(m, (SALEActor, SALECritic, SALEEncoder)) else m.act
         if acts.setdefault(role, act) != act:
             raise NotImplementedError(f"one activation for both critics (got {acts[role]} and {act})")
+        if isinstance(m, MLPCritic):
+            lns.add(bool(getattr(m, "layer_norm", False)))
         if isinstance(m, (SALEActor, SALECritic, SALEEncoder)):
             widths.add((m.hdim, m.zs_dim))
         else:
@@ -188,7 +251,9 @@ def nets_from_make_nn(alg: str, make_nn, state_dim: int, action_dim: int, kwargs
         nets[name] = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in m.state_dict().items()}
     if len(widths) != 1:
         raise NotImplementedError(f"one net shape across the agent's nets (got {sorted(widths)})")
+    if len(lns) > 1:
+        raise NotImplementedError("layer_norm must be the same for both critics (got one with and one without)")
     w = widths.pop()
     if alg == "td7":
-        return w[0], {"zs_dim": w[1]}, nets, acts
-    return w[-1], {"hidden_sizes": list(w)}, nets, acts
+        return w[0], {"zs_dim": w[1]}, nets, acts, False
+    return w[-1], {"hidden_sizes": list(w)}, nets, acts, bool(lns and lns.pop())
