@@ -8,6 +8,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "host.h"
@@ -31,7 +32,9 @@ hipError_t launch_level(const Op* d_ops, const Op* h_ops, int nops, int nwg, hip
 // A captured program.  `launches` is the one description of what a replay runs: the hipGraph was captured
 // from it, rle_plan dispatch 2 launches it on the stream, and dispatch 1 queues it as AQL packets whose
 // kernel arguments are aql_ka's copies.
-struct Graph {
+// Graph owns g and x: move-only, a move leaves the source without handles, the destructor destroys x then g.
+// (The other fields point into the engine's device memory, which outlives every program.)
+struct GraphFields {
   hipGraph_t g = nullptr;
   hipGraphExec_t x = nullptr;
   Op* d_ops = nullptr;
@@ -43,6 +46,28 @@ struct Graph {
   unsigned char* aql_ka = nullptr;    // (rle_plan dispatch 1, untraced) their kernel arguments in device memory, kAqlKaStride apart
   int levels() const { return (int)nops.size(); }
   int nlaunch() const { return (int)launches.size(); }
+};
+struct Graph : GraphFields {
+  Graph() = default;
+  Graph(const Graph&) = delete;
+  Graph& operator=(const Graph&) = delete;
+  Graph(Graph&& o) noexcept : GraphFields(std::move(o)) { o.g = nullptr, o.x = nullptr; }
+  Graph& operator=(Graph&& o) noexcept {
+    if (this != &o) {
+      release();
+      GraphFields::operator=(std::move(o));
+      o.g = nullptr, o.x = nullptr;
+    }
+    return *this;
+  }
+  ~Graph() { release(); }
+
+ private:
+  void release() {
+    if (x) (void)hipGraphExecDestroy(x);
+    if (g) (void)hipGraphDestroy(g);
+    x = nullptr, g = nullptr;
+  }
 };
 constexpr size_t kAqlKaStride = 128;
 

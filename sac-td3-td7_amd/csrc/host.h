@@ -1,4 +1,4 @@
-// Host-side declarations shared by engine.cpp and dispatch.cpp: the error type behind the C ABI's
+// Host-side declarations shared by every host source: the error type behind the C ABI's
 // return codes and the launchers that kernels.hip and replay_norm.hip define.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -804,3 +804,55 @@ def test_wide_tiles_audit_and_hazards(check, monkeypatch):
     e, r, info, _ = _wide_run(512, 3, E.make_plan(wide=1))
     assert ".w]" in e.describe(0)
     assert np.isfinite(info[:, :2]).all()
+
+
+def test_engine_teardown_cycles_on_one_replay():
+    """Engine teardown (the destructor's order, programs that own their graphs): 20 times in one process, on one
+    replay -- create an engine, act_sample at two batch sizes and eval_q (programs built on first use), one burst
+    of 6 taped steps (TD3's 4- and 2-step programs), destroy it; then a second engine on the same replay runs the
+    same burst and is destroyed.  td3_tiny samples uniformly, so the steps leave the replay as it was and every
+    cycle must give the first cycle's results bit for bit.  (This measures no leak.)"""
+    g = load_golden("td3_tiny")
+    alg, env, H, B, Ncap, n_fill, n_steps, use_lap, seed, extra = parse(g)
+    S, A, _ = spec.TASKS[env]
+    assert n_steps >= 6 and not use_lap and not extra
+    first, rep, tp = engine_from_golden(g)
+    cfg = first.cfg
+    first.close()  # (bound, never stepped: unbinds from rep)
+    params = spec.agent_params(alg, S, A, H, seed)
+    rng = np.random.default_rng(5)
+    obs = rng.standard_normal((5, S)).astype(np.float32)
+    act = rng.uniform(-1, 1, (5, A)).astype(np.float32)
+    eps = rng.standard_normal((5, A)).astype(np.float32)
+
+    def burst(acting):
+        eng = E.Engine(cfg)
+        for net, ps in params.items():
+            for name, v in ps.items():
+                eng.set_param(net, name, v)
+        eng.bind(rep)
+        out = {}
+        if acting:
+            out["act_1"] = eng.act_sample(obs[:1], 0).copy()
+            out["act_5"] = eng.act_sample(obs, 2, eps).copy()
+            out["q1"] = eng.eval_q("q1", obs, act)
+        eng.set_tapes(u=tp["u"][:6], eps=tp["eps"][:6])
+        out["info"] = np.asarray(eng.step(6)).copy()
+        out["ind"] = eng.last_indices().copy()
+        for net, ps in params.items():
+            for name in ps:
+                out[net + "." + name] = eng.get_param(net, name).copy()
+        eng.close()
+        return out
+
+    ref = None
+    for cycle in range(20):
+        got = (burst(True), burst(False))
+        ref = ref or got
+        for r, o in zip(ref, got):
+            assert r.keys() == o.keys()
+            for k in r:
+                np.testing.assert_array_equal(o[k], r[k], err_msg=f"cycle {cycle}: {k}")
+    for k in ref[1]:  # (the acting engine's steps are the plain engine's: acting draws nothing the steps read)
+        np.testing.assert_array_equal(ref[0][k], ref[1][k], err_msg=k)
+    assert np.isfinite(ref[0]["info"][:, 0]).all() and np.isfinite(ref[0]["act_5"]).all()

@@ -7,15 +7,20 @@
 NAME: a golden of tests/golden, edge:<case> for a case of tests/edge_cases.py (built under edge_env,
 as tests/test_shape_edges_gpu.py builds it), or offline3:<shape> for an offline TD3 (TD3+BC) engine over a shape
 of tests/test_offline_td3_gpu.py's SHAPES (its _env, offline_engine, ALPHA and tapes: OP_BC modes 2 and 3 and the
-kDwGs weight gradients, which no golden or edge case builds).  Per step: every parameter, the priorities and the
+kDwGs weight gradients, which no golden or edge case builds), or awac:<case> for an offline SAC (AWAC) engine over a
+case of tests/offline_sac_cases.py (test_offline_sac_gpu.offline_engine, the cases' own tapes: OP_AWAC).  Per step: every parameter, the priorities and the
 info row after a single-step replay, and the engine's launch count (launches_<t>: how many rle_level dispatches
 the programs replayed so far took).  The dump also holds the programs' descriptions (rle_graph_describe 0, 1, 3
 and the hard-update program; empty where the engine has none) -- with RLE_DESC_WG=1 in the environment
-they carry every op's workgroup count, so a changed tile plan shows even where the floats agree.
+they carry every op's workgroup count, so a changed tile plan shows even where the floats agree.  After the last
+burst: act_sample on 1 and on 5 seeded observations, mode 0 and mode 2 with a seeded eps (act_<n>_<mode>), eval_q of
+q1 on 5 seeded rows (TD7: the embeddings of fixed_encoder), and the packed state (state_export), so the act, eval and
+state code is compared bit for bit as well.
 
 Environment (dump): BITCMP_BURST steps per rle_step call (6: the multi-step and remainder programs);
 BITCMP_NETS nets to dump; BITCMP_FUSE_OFF the plan's fuse_off, names of rl._engine.FUSE joined by "+" or
-"all" (every fusion that is on by default); BITCMP_WIDE the plan's wide.
+"all" (every fusion that is on by default); BITCMP_WIDE the plan's wide; BITCMP_CLIP a max_norm for
+set_grad_clip; BITCMP_LN=1 for set_layer_norm (TD3 / SAC names only).  The last two apply before the first step.
 
 cmp exits 1 when any array or description differs.  With a third dump (a second run of the first build),
 arrays that differ between the first build's own two runs are reported and left out of the verdict.
@@ -31,6 +36,7 @@ sys.path[:0] = [REPO, os.path.join(REPO, "sac-td3-td7_amd"), os.path.join(REPO, 
 OPT_IN = ("priosample",)  # include/rle.h RLE_FUSE_OPT_IN: off unless asked for, so not part of "all"
 DESCRIBE = {"desc_policy": 0, "desc_plain": 1, "desc_multi": 3, "desc_hard": 2}
 OFFLINE3_STEPS = 6  # steps of an offline3: trajectory (policy steps 1, 3, 5, as the offline TD3 tests run)
+AWAC_STEPS = 12  # steps of an awac: trajectory (SAC's 8-step program, then its 4-step remainder at a burst of 12)
 
 
 def plan_from_env():
@@ -62,6 +68,18 @@ def build(name, plan):
         tapes = T._tapes(OFFLINE3_STEPS, int(g["meta"][1]), A, int(g["meta"][6]))
         g.update({"tape_" + k: v for k, v in tapes.items()})
         return g, eng, rep, S, A
+    if name.startswith("awac:"):
+        import offline_sac_cases as C
+        from test_offline_sac_gpu import offline_engine
+
+        case = name[5:]
+        c = C.CASES[case]
+        eng, rep = offline_engine(case, plan=plan)
+        g = {"meta_alg": "sac", "meta_env": C.ENV, "meta_extra_keys": np.array([], str), "meta_extra_vals": np.array([]),
+             "meta": np.array([c.H, c.B, C.NCAP, C.NCAP, AWAC_STEPS, 0, c.seed]),
+             "_shapes": {net: {k: np.shape(v) for k, v in p.items()} for net, p in C.nets(case).items()}}
+        g.update({"tape_" + k: v for k, v in C.tapes(case, AWAC_STEPS).items()})
+        return g, eng, rep, c.S, c.A
     if not name.startswith("edge:"):
         from conftest import load_golden
 
@@ -87,11 +105,15 @@ def dump(name, steps, out):
     alg, env, H, B, Ncap, n_fill, n_steps, use_lap, seed, extra = parse(g)
     steps = min(steps, n_steps)  # (the golden's tapes cover n_steps)
     tp = {k[5:]: v for k, v in g.items() if k.startswith("tape_")}
-    shapes = {net: {k: np.shape(v) for k, v in p.items()}
-              for net, p in spec.agent_params(alg, S, A, H, seed, **shape_of(g)).items()}
+    shapes = g.pop("_shapes", None) or {net: {k: np.shape(v) for k, v in p.items()}
+                                        for net, p in spec.agent_params(alg, S, A, H, seed, **shape_of(g)).items()}
     keep = os.environ.get("BITCMP_NETS")  # comma-separated nets to dump (default: all)
     if keep:
         shapes = {n: v for n, v in shapes.items() if n in keep.split(",")}
+    if os.environ.get("BITCMP_CLIP"):
+        eng.set_grad_clip(float(os.environ["BITCMP_CLIP"]))
+    if os.environ.get("BITCMP_LN") == "1":
+        eng.set_layer_norm(True)
     res = {k: np.array(eng.describe(which)) for k, which in DESCRIBE.items()}
     eng.set_tapes(u=tp["u"][:steps], eps=tp["eps"][:steps], eps_pi=tp.get("eps_pi"))
     burst = int(os.environ.get("BITCMP_BURST", "1"))  # steps per rle_step call (6: TD7's multi-step graphs)
@@ -103,6 +125,14 @@ def dump(name, steps, out):
         for net, ps in shapes.items():
             for p, shape in ps.items():
                 res[f"{t}/{net}/{p}"] = np.asarray(eng.get_param(net, p)).reshape(shape)
+    rng = np.random.default_rng(20240521)
+    obs, act = rng.standard_normal((5, S)).astype(np.float32), rng.uniform(-1, 1, (5, A)).astype(np.float32)
+    eps = rng.standard_normal((5, A)).astype(np.float32)
+    for n in (1, 5):
+        res[f"act_{n}_0"] = eng.act_sample(obs[:n], 0).copy()
+        res[f"act_{n}_2"] = eng.act_sample(obs[:n], 2, eps[:n]).copy()
+    res["eval_q1"] = eng.eval_q("q1", obs, act, enc="fixed_encoder")
+    res["state_export"] = np.array(eng.state_export())
     np.savez(out, **res)
 
 
