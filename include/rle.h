@@ -298,6 +298,33 @@ int rle_grad_clip_stats(rle_engine* e, float* out6);
  * Not run: an affine LayerNorm, another eps, LayerNorm in the actor, RMSNorm / BatchNorm. */
 int rle_set_layer_norm(rle_engine* e, int critic);
 int rle_get_layer_norm(rle_engine* e, int* critic);
+/* Critic dropout (the DroQ critic: Linear -> Dropout(p) -> LayerNorm -> activation): inverted dropout as
+ * torch.nn.Dropout(p) in train mode on the output z of every hidden Linear of q1, q2 and their targets, ahead of the
+ * LayerNorm, inside the row-norm ops: keep_j = u01(word_j) >= p, zd_j = keep_j ? z_j * s : 0 with s = 1 / (1 - p) in
+ * float32, then the LayerNorm of rle_set_layer_norm on zd; backward dz_j = keep_j ? dzd_j * s : 0.  An all-dropped
+ * row is legal (zd 0, var 0, u 0).  Active in every critic pass of a gradient step -- target, online and policy
+ * pass, AWAC's two forward-only passes -- and off in rle_eval(RLE_EVAL_Q), which is inference.  The H -> 1 output
+ * layer and the actor are unchanged.
+ * The mask: Philox4x32-10 keyed by cfg.seed at counter (b * 128 + j4, 2 + site, step_lo, step_hi); the four output
+ * words are columns 4 j4 .. 4 j4 + 3 of batch row b; step is the RNG step counter (rle_get_counters()[4]) of the
+ * step that consumes the batch, read on the device; site = (pass * 2 + twin) * 8 + layer with pass 0 target,
+ * 1 online, 2 policy (AWAC: Q(s, a_pi)), 3 AWAC's Q(s, a), twin 0 / 1, layer 0 .. RLE_MAX_HIDDEN-1.  The backward
+ * op draws the mask again: nothing is stored, and masks are never taped (rle_set_tapes).
+ * p: 0 <= p < 1 (NaN, negative or >= 1: RLE_EINVAL); 0 is off (default: the LayerNorm programs and their kernel
+ * instance, op for op; p > 0 runs on a kernel instance of its own with the same level counts).  p > 0
+ * needs the critics' LayerNorm on at the call (RLE_EINVAL otherwise: dropout without LayerNorm is not run), and
+ * rle_set_layer_norm(e, 0) while p > 0 is RLE_EINVAL.  TD3 / SAC only (TD7: RLE_EINVAL).  Before the engine's
+ * first step (RLE_ESTATE after it).  Not part of the state: rle_copy_state / rle_copy_nets / rle_state_* work
+ * between engines whose p differ.
+ * Not run: dropout without LayerNorm, dropout in the actor, taped masks. */
+int rle_set_critic_dropout(rle_engine* e, float p);
+int rle_get_critic_dropout(rle_engine* e, float* p);
+/* The mask stream's observable, as rle_replay_fill_random is for its streams: runs the device's mask function (the
+ * one the row ops call) for `rows` batch rows and `width` columns (4 .. 512, a multiple of 4; rows <= 2^20) of
+ * `site` (0 .. 63) at RNG step `step`, with the engine's p, and writes rows x width floats, row-major, each 0
+ * (dropped) or s = 1 / (1 - p) (kept).  With p = 0 (dropout off) every element is kept and the output is all ones.
+ * Syncs. */
+int rle_dropout_mask(rle_engine* e, long long step, int site, int rows, int width, float* out);
 /* Bind the replay the step samples from (the replay_buffer arg of train_ops). */
 int rle_bind_replay(rle_engine* e, rle_replay* r);
 /* Parameter import/export in the reference's state_dict layout (Agent.load_state_dict,
@@ -380,7 +407,9 @@ int rle_step_async(rle_engine* e, int n_steps);
  * eps [n][B][A] (randn_like target noise, or SAC next-state rsample noise), eps_pi [n][B][A]
  * (SAC policy rsample noise; SAC takes eps and eps_pi together), ind [n][B] (explicit
  * indices, e.g. the batch a replay's sample() drew; overrides u).  At least one of u / ind.
- * Pass n_steps = 0 to return to Philox; stepping past the tape's end is an error. */
+ * Pass n_steps = 0 to return to Philox; stepping past the tape's end is an error.
+ * Critic dropout's masks (rle_set_critic_dropout) are never taped: they come from their own Philox stream whatever
+ * the tapes hold, and rle_dropout_mask reads that stream out for a host reference. */
 int rle_set_tapes(rle_engine* e, int n_steps, const float* u, const float* eps, const float* eps_pi,
                   const long long* ind);
 /* Last sampled indices (LAPReplayMemory.ind) [B]. */

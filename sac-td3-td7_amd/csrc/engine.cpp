@@ -194,6 +194,8 @@ struct Engine {
   int kernel_set() const {
     // (LayerNorm critics: OP_LN / OP_LN_BWD are KS_LN's alone; it holds KS_CLIP's code, so they compose with
     // clipping, every activation and both offline modes)
+    // (critic dropout: the row ops' dropout path is KS_DROP's alone -- KS_LN's code with it)
+    if (ln_on() && drop_p > 0.f) return KS_DROP;
     if (ln_on()) return KS_LN;
     // (gradient clipping: EPI_GSQ, the scaled Adam pass over normed operands and OP_CLIP are KS_CLIP's alone; it
     // holds KS_ACT's code, so every activation and offline mode clips)
@@ -219,6 +221,12 @@ struct Engine {
   // and their targets, before the activation (TD3 / SAC)
   bool ln_critic = false;
   bool ln_on() const { return ln_critic; }
+  // Critic dropout (rle_set_critic_dropout): inverted dropout on every hidden Linear's output of the critics, ahead
+  // of the LayerNorm, inside OP_LN / OP_LN_BWD (ops.h LnArgs p).  0: off.  Needs ln_on().  A pass of a gradient step
+  // hands its number to the row ops (drop_site); rle_eval hands none and runs without dropout.
+  float drop_p = 0.f;
+  enum DropPass : int { DROP_TARGET = 0, DROP_ONLINE = 1, DROP_POLICY = 2, DROP_AWAC_DATA = 3, DROP_NONE = -1 };
+  static int drop_site(int pass, int twin, int layer) { return (pass * 2 + twin) * 8 + layer; }
   void resolve_plan() {
     if (plan.steps_per_graph < 0) plan.steps_per_graph = algo == RLE_TD3 ? 16 : algo == RLE_SAC ? 8 : 6;
     // (SAC's target critics' raw-head pre-GEMM consumers: 32 measured +1.0% over 64, 2 pairs)
@@ -1183,6 +1191,10 @@ struct Engine {
     LnOpt() {}
     LnOpt& keep_t(bool on) { return t = on, *this; }
     LnOpt& keep_bwd(View* u_out, View* rstd_out) { return u = u_out, rstd = rstd_out, *this; }
+    // critic dropout on the op's rows: probability p (0: none) at mask site `site` (drop_site)
+    float p = 0.f;
+    int site = 0;
+    LnOpt& drop(float p_, int site_) { return p = p_, site = site_, *this; }
   };
   struct NormBwdOpt {
     bool n = true, t = true;  // output images, as DxOpt's
@@ -1707,8 +1719,10 @@ struct Engine {
     a.nvalid = nvalid;
     a.width = width;
     a.act = act;
+    std::vector<int> rd{z.id};
+    ln_drop(a, o, rd);
     op.wg_count = cdiv(z.rows, 4);  // (one row per wave)
-    pg.add(op, {z.id}, wr);
+    pg.add(op, rd, wr);
     return out;
   }
   View ln_bwd(Prog& pg, const View& dh, const View& u, const View& rstd, int width, int nvalid, int act,
@@ -1729,9 +1743,23 @@ struct Engine {
     a.nvalid = nvalid;
     a.width = width;
     a.act = act;
+    std::vector<int> rd{dh.id, u.id, rstd.id};
+    ln_drop(a, o, rd);
     op.wg_count = cdiv(dh.rows, 4);
-    pg.add(op, {dh.id, u.id, rstd.id}, {out.id});
+    pg.add(op, rd, {out.id});
     return out;
+  }
+  // Critic dropout's fields of a row op: the op then reads the RNG step counter, so it is ordered before the step
+  // end that bumps it (R_CNT), as the noise ops are.  p == 0 leaves the descriptor and the reads as they were.
+  void ln_drop(LnArgs& a, const LnOpt& o, std::vector<int>& rd) {
+    if (!(o.p > 0.f)) return;
+    REQUIRE(o.p < 1.f && o.site >= 0 && o.site < 64 && a.rows <= (1 << 25), "ln: dropout probability / site");
+    a.p = o.p;
+    a.s = 1.0f / (1.0f - o.p);
+    a.site = o.site;
+    a.step = &ctrl->counters[CNT_RNG];
+    a.seed = cfg.seed;
+    rd.push_back(R_CNT);
   }
 
   // AvgL1Norm itself (sale.py:11-13) applied to a normed view: out = x / m (OP_NORMBWD with
@@ -2716,8 +2744,9 @@ struct Engine {
   // The stack with LayerNorm critics (rle_set_layer_norm): per hidden layer the Linear with the identity epilogue
   // (N image only: the norm is its one reader), then OP_LN -- one more level per layer.  M rows, the first nvalid
   // of them real.  us / rs: the normalised rows and rstd of every layer, for the backward (null: forward only).
+  // pass2: critic dropout's pass * 2 + twin of this stack (DROP_*; negative: no dropout -- rle_eval).
   void mlp_critic_fwd_ln(Prog& pg, Net& Q, const View& sv, const View& av, int M, int nvalid, std::vector<View>& hs,
-                         bool out_t, bool last_t = true, std::vector<View>* us = nullptr,
+                         int pass2, bool out_t, bool last_t = true, std::vector<View>* us = nullptr,
                          std::vector<View>* rs = nullptr) {
     const int D = (int)Q.layers.size() - 1;
     hs.assign(D, View{});
@@ -2726,13 +2755,14 @@ struct Engine {
       const View z = i ? fwd(pg, Q.layers[i], {{hs[i - 1]}}, M, ACT_NONE, FwdOpt().no_t())
                        : fwd(pg, Q.layers[0], {{sv}, {av}}, M, ACT_NONE, FwdOpt().no_t());
       hs[i] = ln_fwd(pg, z, Q.layers[i].out, nvalid, actC,
-                     LnOpt().keep_t(out_t && (i < D - 1 || last_t)).keep_bwd(us ? &(*us)[i] : nullptr, us ? &(*rs)[i] : nullptr));
+                     LnOpt().keep_t(out_t && (i < D - 1 || last_t)).keep_bwd(us ? &(*us)[i] : nullptr, us ? &(*rs)[i] : nullptr)
+                         .drop(pass2 < 0 ? 0.f : drop_p, pass2 < 0 ? 0 : pass2 * 8 + i));
     }
   }
   // rle_eval(RLE_EVAL_Q) on a LayerNorm critic: the stack above and the H -> 1 layer
   View mlp_critic_eval_ln(Prog& pg, Net& Q, const View& sv, const View& av, int M, int nvalid) {
     std::vector<View> hs;
-    mlp_critic_fwd_ln(pg, Q, sv, av, M, nvalid, hs, /*out_t*/ false);
+    mlp_critic_fwd_ln(pg, Q, sv, av, M, nvalid, hs, /*pass2 (inference: no dropout)*/ DROP_NONE, /*out_t*/ false);
     return fwd(pg, Q.layers.back(), {{hs.back()}}, M, ACT_NONE);
   }
   // TD3 / SAC: the critic loss head and the actor objective's head fused into the DX of each
@@ -2866,10 +2896,10 @@ struct Engine {
     const bool ln = ln_on();
     REQUIRE(!ln || !o.hdx, "LayerNorm critics: the heads run stand-alone");
     for (int n = 0; n < 2; ++n)  // (forward only)
-      if (ln) mlp_critic_fwd_ln(pg, *tq[n], sb.s2, ac.a_next, B, Bv, th[n], /*out_t*/ false);
+      if (ln) mlp_critic_fwd_ln(pg, *tq[n], sb.s2, ac.a_next, B, Bv, th[n], DROP_TARGET * 2 + n, /*out_t*/ false);
       else mlp_critic_fwd(pg, *tq[n], sb.s2, ac.a_next, th[n], /*out_t*/ false, ac.tpre(), true, o.hdx);
     for (int n = 0; n < 2; ++n)
-      if (ln) mlp_critic_fwd_ln(pg, *q[n], sb.s, act_in, B, Bv, o.c[n], /*out_t*/ true, true, &o.cz[n], &o.crs[n]);
+      if (ln) mlp_critic_fwd_ln(pg, *q[n], sb.s, act_in, B, Bv, o.c[n], DROP_ONLINE * 2 + n, /*out_t*/ true, true, &o.cz[n], &o.crs[n]);
       else mlp_critic_fwd(pg, *q[n], sb.s, act_in, o.c[n], /*out_t*/ true, nullptr, true, o.hdx, &o.cz[n]);
     // (the loss head's derivative rows: ELU' reads the pre-activation; ReLU' / identity the output.  LayerNorm
     // critics: the head leaves dh = dq w, no derivative -- OP_LN_BWD takes act' from u)
@@ -2915,7 +2945,8 @@ struct Engine {
         // which the layer's weight gradient (T image) and the next input gradient (N image) read
         View dh = cr.dz1[n];
         for (int i = D - 1; i >= 0; --i) {
-          const View dzi = ln_bwd(pg, dh, cr.cz[n][i], cr.crs[n][i], Q.layers[i].out, Bv, actC, LnOpt().keep_t(true));
+          const View dzi = ln_bwd(pg, dh, cr.cz[n][i], cr.crs[n][i], Q.layers[i].out, Bv, actC,
+                                  LnOpt().keep_t(true).drop(drop_p, drop_site(DROP_ONLINE, n, i)));
           if (i) dh = dx(pg, {{dzi, &Q.layers[i], 0}}, HS[i - 1], B, DxOpt().no_t());
           if (i) dw(pg, Q.layers[i], dzi, {cr.c[n][i - 1]}, B, CNT_ADAM_Q, cfg.critic_lr, qo);
           else dw(pg, Q.layers[0], dzi, {sb.s, act_in}, B, CNT_ADAM_Q, cfg.critic_lr, qo);
@@ -2947,7 +2978,7 @@ struct Engine {
     std::vector<View> pc[2], pcz[2], prs[2];  // (LayerNorm critics: pcz holds u, prs rstd)
     for (int n = 0; n < 2; ++n)
       // (LayerNorm critics: no T image at all -- no weight gradient here, and no input gradient reads a mask)
-      if (ln) mlp_critic_fwd_ln(pg, *q[n], s, a_pi, B, Bv, pc[n], /*out_t*/ false, false, &pcz[n], &prs[n]);
+      if (ln) mlp_critic_fwd_ln(pg, *q[n], s, a_pi, B, Bv, pc[n], DROP_POLICY * 2 + n, /*out_t*/ false, false, &pcz[n], &prs[n]);
       else mlp_critic_fwd(pg, *q[n], s, a_pi, pc[n], /*out_t*/ true, nullptr, /*last_t*/ false, hdx, &pcz[n]);
     const View p1[2] = {pc[0][D - 1], pc[1][D - 1]};
     // (no weight gradient of the critics in the policy pass: the gradients keep N images only)
@@ -2999,7 +3030,8 @@ struct Engine {
     for (int n = 0; n < 2 && ln; ++n) {
       View dh = dzp1[n];
       for (int i = D - 1; i >= 0; --i) {
-        dzp0[n] = ln_bwd(pg, dh, pcz[n][i], prs[n][i], q[n]->layers[i].out, Bv, actC);
+        dzp0[n] = ln_bwd(pg, dh, pcz[n][i], prs[n][i], q[n]->layers[i].out, Bv, actC,
+                         LnOpt().drop(drop_p, drop_site(DROP_POLICY, n, i)));
         if (i) dh = dx(pg, {{dzp0[n], &q[n]->layers[i], 0}}, HS[i - 1], B, po);
       }
     }
@@ -3065,8 +3097,8 @@ struct Engine {
     for (int n = 0; n < 2; ++n) {
       std::vector<View> hd, hv;
       if (ln_on()) {
-        mlp_critic_fwd_ln(pg, *q[n], sb.s, act_in, B, Bv, hd, /*out_t*/ false);
-        mlp_critic_fwd_ln(pg, *q[n], sb.s, ac.a_pi, B, Bv, hv, /*out_t*/ false);
+        mlp_critic_fwd_ln(pg, *q[n], sb.s, act_in, B, Bv, hd, DROP_AWAC_DATA * 2 + n, /*out_t*/ false);
+        mlp_critic_fwd_ln(pg, *q[n], sb.s, ac.a_pi, B, Bv, hv, DROP_POLICY * 2 + n, /*out_t*/ false);
       } else {
         mlp_critic_fwd(pg, *q[n], sb.s, act_in, hd, /*out_t*/ false);
         mlp_critic_fwd(pg, *q[n], sb.s, ac.a_pi, hv, /*out_t*/ false);
@@ -3297,8 +3329,8 @@ struct Engine {
         G.desc += std::string(" ") + (pg.crit_lv[l][k] ? "*" : "") +
                   (op.kind == OP_AWAC   ? "awac"
                    : op.kind == OP_CLIP ? "clip"
-                   : op.kind == OP_LN   ? "ln"
-                   : op.kind == OP_LN_BWD ? "ln-bwd"
+                   : op.kind == OP_LN   ? (op.ln.p > 0.f ? "ln+drop" : "ln")
+                   : op.kind == OP_LN_BWD ? (op.ln.p > 0.f ? "ln-bwd+drop" : "ln-bwd")
                                           : kname[op.kind]);
         if (op.kind == OP_GEMM) {
           static const char* kepi[] = {"st", "adam", "mse", "qhead", "nbdot", "act", "qdot", "sacbwd", "sacfwd", "gsq"};
@@ -3905,6 +3937,9 @@ int rle_set_layer_norm(rle_engine* h, int critic) {
     Engine& e = drained(h);
     REQUIRE(e.algo != RLE_TD7 || !critic,
             "set_layer_norm: TD3 / SAC only (TD7's SALE critics already carry AvgL1Norm)");
+    REQUIRE(critic || !(e.drop_p > 0.f),
+            "set_layer_norm: critic dropout is on and lives in the row-norm ops (dropout without LayerNorm is not "
+            "run; rle_set_critic_dropout(e, 0) first)");
     if (e.built)
       throw Error{RLE_ESTATE, "set_layer_norm: the engine has already built its step programs (set it before the "
                               "first step)"};
@@ -3923,6 +3958,50 @@ int rle_get_layer_norm(rle_engine* h, int* critic) {
   return guard([&] {
     REQUIRE(h && critic, "get_layer_norm: null");
     *critic = h->e->ln_critic ? 1 : 0;
+  });
+}
+
+int rle_set_critic_dropout(rle_engine* h, float p) {
+  return guard([&] {
+    REQUIRE(h, "set_critic_dropout: null");
+    REQUIRE(p >= 0.f && p < 1.f, "set_critic_dropout: p must be in [0, 1) (0: off)");  // (NaN fails too)
+    Engine& e = drained(h);
+    REQUIRE(e.algo != RLE_TD7 || !(p > 0.f), "set_critic_dropout: TD3 / SAC only (as rle_set_layer_norm)");
+    if (e.built)
+      throw Error{RLE_ESTATE, "set_critic_dropout: the engine has already built its step programs (set it before "
+                              "the first step)"};
+    REQUIRE(e.ln_on() || !(p > 0.f),
+            "set_critic_dropout: the critics' LayerNorm is off (rle_set_layer_norm(e, 1) first): the dropout lives in "
+            "the row-norm ops, dropout without LayerNorm is not run");
+    e.drop_p = p;  // (rle_eval's forward programs run without dropout: none to rebuild)
+  });
+}
+
+int rle_get_critic_dropout(rle_engine* h, float* p) {
+  return guard([&] {
+    REQUIRE(h && p, "get_critic_dropout: null");
+    *p = h->e->drop_p;
+  });
+}
+
+int rle_dropout_mask(rle_engine* h, long long step, int site, int rows, int width, float* out) {
+  return guard([&] {
+    REQUIRE(h && out, "dropout_mask: null");
+    REQUIRE(site >= 0 && site < 64, "dropout_mask: site is (pass * 2 + twin) * 8 + layer, 0 .. 63");
+    REQUIRE(rows >= 1 && rows <= (1 << 20) && width >= 4 && width <= 512 && width % 4 == 0,
+            "dropout_mask: rows 1 .. 2^20, width 4 .. 512 in steps of 4");
+    Engine& e = drained(h);
+    HIPCHK(hipSetDevice(e.cfg.device));
+    const size_t bytes = (size_t)rows * width * sizeof(float);
+    float* d = nullptr;
+    HIPCHK(hipMalloc(&d, bytes));
+    const float p = e.drop_p, s = 1.0f / (1.0f - p);
+    hipError_t rc = rle::launch_dropout_mask(d, rows, width, (unsigned long long)e.cfg.seed, (unsigned long long)step,
+                                             site, p, s, e.stream);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(e.stream);
+    if (rc == hipSuccess) rc = hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    HIPCHK(rc);
   });
 }
 

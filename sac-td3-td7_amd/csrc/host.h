@@ -43,6 +43,9 @@ hipError_t launch_replay_pack(const ReplayPackArgs& a, hipStream_t st);
 hipError_t launch_replay_unpack(const ReplayPackArgs& a, hipStream_t st);
 hipError_t launch_state_pack(const StatePackArgs& a, hipStream_t st);
 hipError_t launch_state_unpack(const StatePackArgs& a, hipStream_t st);
+// (drop_level.hip: the critic dropout's mask stream, [rows][width] row-major, 0 or s; rows <= 2^20, width as LnArgs')
+hipError_t launch_dropout_mask(float* out, int rows, int width, unsigned long long seed, unsigned long long step,
+                               int site, float p, float s, hipStream_t st);
 // ---- replay_norm.hip
 hipError_t launch_replay_colsum(const ReplayStatArgs& a, hipStream_t st);
 hipError_t launch_replay_colfin(const ReplayStatArgs& a, hipStream_t st);

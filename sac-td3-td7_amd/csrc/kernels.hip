@@ -2362,13 +2362,33 @@ __device__ __forceinline__ void op_normbwd(const CAS NormBwdArgs& a, int t) {
   if (in1) mat_str4(a.dx, row, c1, f(g1, x1));
 }
 
-// ---------------------------------------------------------------- LayerNorm critics (ops.h LnArgs; KS_LN alone)
+// ---------------------------------------------------------------- LayerNorm critics (ops.h LnArgs; KS_LN, KS_DROP)
 
 // One row per wave (4 per workgroup), lane l holding columns 4l..4l+3 (+256 in the second pass, width > 256) as
 // float4s of the N images, as op_normbwd.  in*: the lane's float4 holds valid columns (width is a multiple of 4, so
 // whole float4s); st*: it lies inside the 16-padded width and is stored -- as zero where it is not valid.
 // BWD false: OP_LN, h = act((z - mu) rstd).  BWD true: OP_LN_BWD, dz from dh, u and rstd.
-template <bool BWD>
+//
+// Critic dropout (LnArgs p > 0): drop_mask4 gives the keep-and-scale factors of the float4 at columns 4 j4 .. of
+// batch row b -- s where u01(word) >= p, else 0 -- from one Philox block at counter (b * 128 + j4, 2 + site, step);
+// the forward op applies them to z right after the load, the backward op draws them again and applies them to dz
+// before the store.  drop_apply is a select per element (v * s rounded once, an exact 0 where dropped).
+// rle_dropout_mask_kernel (drop_level.hip's translation unit) stores the same function's factors for the host.
+// DROP: the instance compiles the dropout path (KS_DROP); without it (KS_LN) the op is the one it was.
+__device__ __forceinline__ float4 drop_mask4(unsigned long long seed, unsigned long long step, int site, int b, int j4,
+                                             float p, float s) {
+  const uint2 key = make_uint2((unsigned)seed, (unsigned)(seed >> 32));
+  const uint4 r = philox(key, make_uint4((unsigned)b * 128u + (unsigned)j4, 2u + (unsigned)site, (unsigned)step,
+                                         (unsigned)(step >> 32)));
+  return make_float4(u01(r.x) >= p ? s : 0.f, u01(r.y) >= p ? s : 0.f, u01(r.z) >= p ? s : 0.f,
+                     u01(r.w) >= p ? s : 0.f);
+}
+__device__ __forceinline__ float4 drop_apply(float4 v, float4 k) {
+  return make_float4(k.x != 0.f ? __fmul_rn(v.x, k.x) : 0.f, k.y != 0.f ? __fmul_rn(v.y, k.y) : 0.f,
+                     k.z != 0.f ? __fmul_rn(v.z, k.z) : 0.f, k.w != 0.f ? __fmul_rn(v.w, k.w) : 0.f);
+}
+
+template <bool BWD, bool DROP>
 __device__ __forceinline__ void op_ln(const CAS LnArgs& a, int t) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int row = t * 4 + wave;
@@ -2386,7 +2406,18 @@ __device__ __forceinline__ void op_ln(const CAS LnArgs& a, int t) {
     return s;
   };
   auto mul = [](float4 p, float4 q) { return make_float4(p.x * q.x, p.y * q.y, p.z * q.z, p.w * q.w); };
-  const float4 x0 = in0 ? mat_ldr4(a.x, row, c0) : zero, x1 = in1 ? mat_ldr4(a.x, row, c1) : zero;
+  float4 x0 = in0 ? mat_ldr4(a.x, row, c0) : zero, x1 = in1 ? mat_ldr4(a.x, row, c1) : zero;
+  // (critic dropout: wave-uniform in everything but j4; one Philox block per float4, the second for widths > 256)
+  const bool drop = DROP && a.p > 0.f;
+  float4 k0 = zero, k1 = zero;
+  if constexpr (DROP) {
+    if (drop) {
+      const unsigned long long step = (unsigned long long)sload(a.step);
+      k0 = drop_mask4(a.seed, step, a.site, row, lane, a.p, a.s);
+      if (a.width > 256) k1 = drop_mask4(a.seed, step, a.site, row, lane + 64, a.p, a.s);
+      if constexpr (!BWD) x0 = drop_apply(x0, k0), x1 = drop_apply(x1, k1);
+    }
+  }
   if constexpr (!BWD) {
     const float mu = wave_sum(lsum(x0, x1)) / (float)a.width;
     auto ctr = [&](float4 p) { return make_float4(p.x - mu, p.y - mu, p.z - mu, p.w - mu); };
@@ -2419,8 +2450,15 @@ __device__ __forceinline__ void op_ln(const CAS LnArgs& a, int t) {
       return make_float4(rstd * ((g.x - m1) - u.x * m2), rstd * ((g.y - m1) - u.y * m2), rstd * ((g.z - m1) - u.z * m2),
                          rstd * ((g.w - m1) - u.w * m2));
     };
-    if (st0) mat_str4(a.y, row, c0, in0 ? dz(g0, u0) : zero);
-    if (st1) mat_str4(a.y, row, c1, in1 ? dz(g1, u1) : zero);
+    if constexpr (DROP) {
+      float4 r0 = in0 ? dz(g0, u0) : zero, r1 = in1 ? dz(g1, u1) : zero;
+      if (drop) r0 = drop_apply(r0, k0), r1 = drop_apply(r1, k1);
+      if (st0) mat_str4(a.y, row, c0, r0);
+      if (st1) mat_str4(a.y, row, c1, r1);
+    } else {
+      if (st0) mat_str4(a.y, row, c0, in0 ? dz(g0, u0) : zero);
+      if (st1) mat_str4(a.y, row, c1, in1 ? dz(g1, u1) : zero);
+    }
   }
 }
 
@@ -3568,10 +3606,10 @@ __global__ __launch_bounds__(kThreads, RLE_WAVES) void rle_level(unsigned e0, un
     RLE_OP(0, if (ks_family(KS) != KS_MLP && vid == (OP_BC >> 4)) op_bc<ks_family(KS) == KS_EXT>(op.bc, t, smem);
            else if (ks_family(KS) == KS_EXT && vid == (OP_AWAC >> 4)) op_awac(op.awac, t, smem);
            else if (ks_clip(KS) && vid == (OP_CLIP >> 4)) op_clip(op.clip, smem);
-           // (OP_LN / OP_LN_BWD, LayerNorm critics: the KS_LN instance's alone)
-           else if constexpr (KS == KS_LN) {
-             if (vid == (OP_LN >> 4)) op_ln<false>(op.ln, t);
-             else if (vid == (OP_LN_BWD >> 4)) op_ln<true>(op.ln, t);
+           // (OP_LN / OP_LN_BWD, LayerNorm critics: the KS_LN instance's, and KS_DROP's with the dropout path)
+           else if constexpr (ks_ln(KS)) {
+             if (vid == (OP_LN >> 4)) (op_ln<false, KS == KS_DROP>)(op.ln, t);
+             else if (vid == (OP_LN_BWD >> 4)) (op_ln<true, KS == KS_DROP>)(op.ln, t);
            })
 #undef RLE_OP
     default: break;
@@ -3581,8 +3619,9 @@ __global__ __launch_bounds__(kThreads, RLE_WAVES) void rle_level(unsigned e0, un
 
 // clip_level.hip compiles this file up to here (RLE_CLIP_TU) for the KS_CLIP instance alone: a code object of its
 // own, so this translation unit's -- every other instance and the stand-alone kernels below -- is the one it was
-// before clipped programs existed, down to the kernels' addresses.  ln_level.hip (RLE_LN_TU) does the same for KS_LN.
-#if !defined(RLE_CLIP_TU) && !defined(RLE_LN_TU)
+// before clipped programs existed, down to the kernels' addresses.  ln_level.hip (RLE_LN_TU) does the same for KS_LN,
+// drop_level.hip (RLE_DROP_TU) for KS_DROP.
+#if !defined(RLE_CLIP_TU) && !defined(RLE_LN_TU) && !defined(RLE_DROP_TU)
 
 // ---------------------------------------------------------------- B = 1 act chain (ops.h ActChainArgs)
 // Row block rb of layer L in registers: column block cb = wave + 4 i of the [16][K] strip, lane l
@@ -4067,9 +4106,11 @@ int trace_stride() { return kTraceStride; }
   X(KS_EXT, "_ZN3rle9rle_levelILb0ELi2EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd")  \
   X(KS_TD7W, "_ZN3rle9rle_levelILb0ELi3EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd") \
   X(KS_ACT, "_ZN3rle9rle_levelILb0ELi4EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd")
-// (KS_CLIP, KS_LN: the last two KernelSets, instantiated in clip_level.hip and ln_level.hip)
+// (KS_CLIP, KS_LN, KS_DROP: the last three KernelSets, instantiated in clip_level.hip, ln_level.hip and drop_level.hip)
 const void* clip_level_fn(int traced);
 const void* ln_level_fn(int traced);
+const void* drop_level_fn(int traced);
+constexpr const char* kDropLevelSymbol = "_ZN3rle9rle_levelILb0ELi7EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd";
 constexpr const char* kClipLevelSymbol = "_ZN3rle9rle_levelILb0ELi5EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd";
 constexpr const char* kLnLevelSymbol = "_ZN3rle9rle_levelILb0ELi6EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd";
 constexpr int kLevelRows = KS_CLIP;  // instances of this translation unit
@@ -4088,11 +4129,14 @@ constexpr bool level_rows_follow_enum() {
     if (kLevelRowKs[i] != i) return false;
   return true;
 }
-static_assert(sizeof(kLevelRowKs) == kLevelRows * sizeof(int) && level_rows_follow_enum() && KS_CLIP + 2 == KS_COUNT &&
-                  KS_LN + 1 == KS_COUNT,
-              "RLE_LEVEL_INSTANCES: one row per KernelSet but the last two, in the enum's order");
+static_assert(sizeof(kLevelRowKs) == kLevelRows * sizeof(int) && level_rows_follow_enum() && KS_CLIP + 3 == KS_COUNT &&
+                  KS_LN + 2 == KS_COUNT && KS_DROP + 1 == KS_COUNT,
+              "RLE_LEVEL_INSTANCES: one row per KernelSet but the last three, in the enum's order");
 static const void* level_fn(int traced, int ks) {
-  return ks == KS_CLIP ? clip_level_fn(traced) : ks == KS_LN ? ln_level_fn(traced) : kLevel.fn[traced][ks];
+  return ks == KS_CLIP ? clip_level_fn(traced)
+         : ks == KS_LN ? ln_level_fn(traced)
+         : ks == KS_DROP ? drop_level_fn(traced)
+                         : kLevel.fn[traced][ks];
 }
 #undef RLE_ROW_KS
 #undef RLE_ROW_FN
@@ -4114,7 +4158,7 @@ int level_capacity() {
 }
 
 const char* level_kernel_symbol(int ks) {
-  return ks == KS_CLIP ? kClipLevelSymbol : ks == KS_LN ? kLnLevelSymbol : kLevel.symbol[ks];
+  return ks == KS_CLIP ? kClipLevelSymbol : ks == KS_LN ? kLnLevelSymbol : ks == KS_DROP ? kDropLevelSymbol : kLevel.symbol[ks];
 }
 
 // Launches the instance the packet names with the packet's own argument bytes.
@@ -4191,10 +4235,37 @@ const void* clip_level_fn(int traced) {
   return traced ? (const void*)rle_level<true, KS_CLIP> : (const void*)rle_level<false, KS_CLIP>;
 }
 
-#else  // RLE_LN_TU
+#elif defined(RLE_LN_TU)
 
 const void* ln_level_fn(int traced) {
   return traced ? (const void*)rle_level<true, KS_LN> : (const void*)rle_level<false, KS_LN>;
+}
+
+#else  // RLE_DROP_TU
+
+const void* drop_level_fn(int traced) {
+  return traced ? (const void*)rle_level<true, KS_DROP> : (const void*)rle_level<false, KS_DROP>;
+}
+
+// rle_dropout_mask: the critic dropout's mask stream as the row ops draw it (drop_mask4), one thread per float4 of
+// a row-major [rows][width] array: 0 where the unit is dropped, s where it is kept.  It lives here, beside the one
+// instance that calls drop_mask4, so the code objects of kernels.hip, clip_level.hip and ln_level.hip hold no new kernel.
+__global__ void rle_dropout_mask_kernel(float* out, int rows, int width, unsigned long long seed,
+                                        unsigned long long step, int site, float p, float s) {
+  const int w4 = width >> 2;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)rows * w4) return;
+  const int b = (int)(i / w4), j4 = (int)(i - (long long)b * w4);
+  st4g(GW(out) + (size_t)i * 4, drop_mask4(seed, step, site, b, j4, p, s));
+}
+hipError_t launch_dropout_mask(float* out, int rows, int width, unsigned long long seed, unsigned long long step,
+                               int site, float p, float s, hipStream_t st) {
+  if (!out || rows < 1 || rows > (1 << 20) || width < 4 || width > 512 || width % 4 || site < 0 || site >= 64)
+    return hipErrorInvalidValue;
+  const long long n4 = (long long)rows * (width >> 2);
+  hipLaunchKernelGGL(rle_dropout_mask_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, out, rows, width,
+                     seed, step, site, p, s);
+  return hipGetLastError();
 }
 
 #endif

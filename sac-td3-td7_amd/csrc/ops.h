@@ -36,8 +36,8 @@ enum OpKind : int {
   OP_BC = 16,           // TD7 offline: the behaviour-cloning term's scalars and action-gradient operand (BcArgs)
   OP_AWAC = 32,         // offline SAC: the advantage-weighted policy step's row-wise op (AwacArgs; the extended instance)
   OP_CLIP = 48,         // gradient clipping: an optimizer's global norm and clip coefficient (ClipArgs; KS_CLIP alone)
-  OP_LN = 64,           // LayerNorm critics: a hidden layer's row norm and activation (LnArgs; KS_LN alone)
-  OP_LN_BWD = 80,       // ... and its backward, dh -> dz (LnArgs; KS_LN alone)
+  OP_LN = 64,           // LayerNorm critics: a hidden layer's row norm and activation (LnArgs; KS_LN / KS_DROP)
+  OP_LN_BWD = 80,       // ... and its backward, dh -> dz (LnArgs; KS_LN / KS_DROP)
 };
 
 // ---------------------------------------------------------------- tensor images
@@ -244,10 +244,14 @@ constexpr bool wide_variant(int mode, int epi, int pk) {
 // on -- again a set and (ln_level.hip) a code object of its own, so every other instance is the code it was, where
 // it was.  It holds KS_CLIP's code, so LayerNorm composes with every activation, both offline modes and clipping.
 enum KernelSet : int {
-  KS_TD7 = 0, KS_MLP = 1, KS_EXT = 2, KS_TD7W = 3, KS_ACT = 4, KS_CLIP = 5, KS_LN = 6, KS_COUNT = 7
+  KS_TD7 = 0, KS_MLP = 1, KS_EXT = 2, KS_TD7W = 3, KS_ACT = 4, KS_CLIP = 5, KS_LN = 6, KS_DROP = 7, KS_COUNT = 8
 };
+// KS_DROP: KS_LN's code with the row ops' critic-dropout path compiled in (LnArgs p > 0), for engines with
+// rle_set_critic_dropout on -- once more a set and (drop_level.hip) a code object of its own: KS_LN compiles the
+// row ops without that path, so ln_level.hip's code object is the one it was before critic dropout existed.
+constexpr bool ks_ln(int ks) { return ks == KS_LN || ks == KS_DROP; }
 // the instances that hold the clipped programs' code (EPI_GSQ, the sets-4 variants, OP_CLIP)
-constexpr bool ks_clip(int ks) { return ks == KS_CLIP || ks == KS_LN; }
+constexpr bool ks_clip(int ks) { return ks == KS_CLIP || ks == KS_LN || ks == KS_DROP; }
 // the agent family whose variants (RLE_GEMM_VARIANTS sets bit) and ops an instance compiles
 constexpr int ks_family(int ks) { return ks == KS_TD7W ? KS_TD7 : ks == KS_ACT || ks_clip(ks) ? KS_EXT : ks; }
 // the instances that dispatch an ELU id a second time on the op's activation (kActRt: LeakyReLU / SiLU / GELU)
@@ -674,6 +678,13 @@ struct ClipArgs {
 // plus that of the second -- followed by one wave_sum: the order depends on `width` alone.  Columns in
 // [width, 16-padded width) enter no sum and are stored as zero in h, u and dz; rows in [nvalid, rows) are stored as
 // zero, rstd 0.  A constant row has var 0 and the finite rstd 1 / sqrt(1e-5).  No parameter is read or written.
+// Critic dropout (rle_set_critic_dropout, p > 0, the KS_DROP instance; p == 0 is the path above): inverted dropout on z
+// ahead of the norm,
+//   keep_j = u01(word_j) >= p,  zd_j = keep_j ? z_j * s : 0  (s = 1 / (1 - p), one rounding),  OP_LN on zd;
+//   OP_LN_BWD  dz_j = keep_j ? dzd_j * s : 0,  dzd the result above
+// word_j: Philox keyed by `seed` at counter (b * 128 + j4, 2 + site, step_lo, step_hi), b the row, j4 = j / 4, the
+// four output words the four columns of that float4; step = *step, read on the device.  Both ops draw the mask from
+// the counter: nothing is stored.  An all-dropped row is a constant row (zd 0, var 0, u 0).
 struct LnArgs {
   Mat x;                 // OP_LN: z, the Linear's output (N image).  OP_LN_BWD: dh (N image)
   Mat y;                 // OP_LN: h out (N; T where a weight gradient reads it).  OP_LN_BWD: dz out (N; T likewise)
@@ -681,6 +692,10 @@ struct LnArgs {
   float* rstd;           // [rows]: OP_LN out (null in a forward-only pass), OP_LN_BWD in
   int rows, nvalid;      // rows: a multiple of 16, every one stored
   int width, act;        // width: 4 .. 512, a multiple of 4; act: the hidden activation (ACT_*), run-time
+  float p, s;            // critic dropout: the drop probability (0: none) and 1 / (1 - p)
+  int site;              // ... (pass * 2 + twin) * 8 + layer: the mask stream's counter word .y is 2 + site
+  const long long* step; // ... the step counter the noise ops read (SampleArgs::ctrl_rng)
+  unsigned long long seed;  // ... cfg.seed, the stream's key
 };
 
 struct FlatArgs {   // POLYAK / COPY / MAXRED

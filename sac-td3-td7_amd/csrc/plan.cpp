@@ -272,6 +272,13 @@ static void audit_ln(const Op& op, const AllocRegistry& allocs) {
   if (bwd || a.u.n) mat(a.u, true, "ln u");
   if (bwd || a.rstd) range(a.rstd, 0, (long long)a.rows * 4, "ln rstd");
   if (!bwd && !a.u.n != !a.rstd) fail("ln u / rstd (kept together)");
+  // (critic dropout: the probability, the site -- counter word .y = 2 + site stays clear of the step streams' 0 and
+  // 1 -- the row count b * 128 + j4 fits a word with, and the step counter it reads)
+  if (!(a.p >= 0.f && a.p < 1.f)) fail("ln dropout p");
+  if (a.p > 0.f) {
+    if (a.site < 0 || a.site >= 64 || a.rows > (1 << 25) || a.s != 1.0f / (1.0f - a.p)) fail("ln dropout site / scale");
+    range(a.step, 0, 8, "ln dropout step counter");
+  }
 }
 
 void GemmAudit::audit_range(const void* base, long long lo, long long bytes, const char* what, const GemmArgs& g,
@@ -822,6 +829,7 @@ void OpAccesses::op_accesses(const Op& op, std::vector<Access>& v) const {
       acc_mat(v, a.y, 1, bwd ? "ln-bwd dz" : "ln h");
       acc_mat(v, a.u, bwd ? 0 : 1, "ln u");
       acc_bytes(v, a.rstd, (long long)a.rows * 4, bwd ? 0 : 1, "ln rstd");
+      if (a.p > 0.f) acc_bytes(v, a.step, 8, 0, "rng step");  // (critic dropout: the mask stream's step word)
       break;
     }
     case OP_FOLDBIAS: {

@@ -182,6 +182,9 @@ SIGNATURES = {
     "rle_grad_clip_stats": (_int, [_vp, _f32p]),
     "rle_set_layer_norm": (_int, [_vp, _int]),
     "rle_get_layer_norm": (_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
+    "rle_set_critic_dropout": (_int, [_vp, ctypes.c_float]),
+    "rle_get_critic_dropout": (_int, [_vp, _f32p]),
+    "rle_dropout_mask": (_int, [_vp, _ll, _int, _int, _int, _f32p]),
     "rle_bind_replay": (_int, [_vp, _vp]),
     "rle_param_numel": (_int, [_vp, _cs, _cs, _i64p]),
     "rle_get_param": (_int, [_vp, _cs, _cs, _f32p, _ll]),
@@ -431,6 +434,27 @@ class Engine:
         v = ctypes.c_int(0)
         _check(lib().rle_get_layer_norm(self.h, ctypes.byref(v)))
         return bool(v.value)
+
+    def set_critic_dropout(self, p: float):
+        """Inverted dropout (torch.nn.Dropout(p) in train mode) on every hidden Linear's output of the critics and
+        their targets, ahead of the LayerNorm, in every critic pass of a gradient step; off in eval_q.  0 <= p < 1,
+        0 off.  Needs set_layer_norm(True).  Before the first step."""
+        _check(lib().rle_set_critic_dropout(self.h, ctypes.c_float(p)))
+
+    def critic_dropout(self) -> float:
+        """The critics' dropout probability (rle_get_critic_dropout; 0: off)."""
+        v = np.zeros(1, np.float32)
+        _check(lib().rle_get_critic_dropout(self.h, _fp(v)))
+        return float(v[0])
+
+    def dropout_mask(self, step: int, site: int, rows: int, width: int) -> np.ndarray:
+        """The device's dropout mask of `site` = (pass * 2 + twin) * 8 + layer at RNG step `step`: float32
+        [rows, width], 0 where dropped, 1 / (1 - p) where kept (rle_dropout_mask)."""
+        out = np.empty((rows, width), np.float32)
+        step = int(step) & 0xFFFFFFFFFFFFFFFF
+        _check(lib().rle_dropout_mask(self.h, ctypes.c_longlong(step - (1 << 64) if step >> 63 else step),
+                                      ctypes.c_int(site), ctypes.c_int(rows), ctypes.c_int(width), _fp(out)))
+        return out
 
     def close(self):
         if self.h:

@@ -38,22 +38,34 @@ class EngineAgent(Agent, Sampler):
     clip_grad_norm: float = math.inf
     # parameter-free LayerNorm after every hidden Linear of the critics (rle_set_layer_norm; TD3 / SAC)
     critic_layer_norm: bool = False
+    # dropout probability on every hidden Linear's output of the critics, ahead of the LayerNorm
+    # (rle_set_critic_dropout; TD3 / SAC, needs critic_layer_norm); 0.0: off
+    critic_dropout: float = 0.0
 
     def _setup(self, env_id, *, hidden, batch_size, seed, device, make_nn, make_nn_kwargs, cfg):
         custom = None
         shape = {}  # net shapes beyond the defaults: zs_dim (SALE), hidden_sizes (make_mlp)
         acts = {}  # hidden activations of the make_nn nets (make_config act_*)
         if make_nn is not None:  # td7.py:56-61 / td3.py:53-56 / sac.py:47-50 (rl.nn.modules nets only)
-            from rl.nn.modules import nets_from_make_nn
+            from rl.nn.modules import nets_and_settings_from_make_nn
 
             S, A = get_state_action_dims(env_id)
-            hidden, shape, custom, acts, ln = nets_from_make_nn(self.ALG, make_nn, S, A, make_nn_kwargs)
+            hidden, shape, custom, acts, ln, drop = nets_and_settings_from_make_nn(self.ALG, make_nn, S, A,
+                                                                                    make_nn_kwargs)
             if self.critic_layer_norm and not ln:
                 raise ValueError("critic_layer_norm=True, but make_nn's critics carry no LayerNorm "
                                  "(rl.nn.MLPCritic(..., layer_norm=True))")
             if ln:  # (the hook's nets decide; False stays the class default)
                 self.critic_layer_norm = True
+            if self.critic_dropout and drop != self.critic_dropout:
+                raise ValueError(f"critic_dropout={self.critic_dropout}, but make_nn's critics carry dropout {drop} "
+                                 "(rl.nn.MLPCritic(..., layer_norm=True, dropout=p))")
+            if drop:  # (the hook's nets decide; 0.0 stays the class default)
+                self.critic_dropout = float(drop)
             make_nn_kwargs = {}
+        if self.critic_dropout and not self.critic_layer_norm:
+            raise ValueError("critic_dropout needs critic_layer_norm=True: the dropout lives in the critics' "
+                             "LayerNorm blocks (dropout without LayerNorm is not run)")
         hdim = make_nn_kwargs.pop("hdim", None)
         zs = make_nn_kwargs.pop("zs_dim", None)
         hs = make_nn_kwargs.pop("hidden_sizes", None)
@@ -112,7 +124,19 @@ class EngineAgent(Agent, Sampler):
             eng.set_grad_clip(clip)
         if getattr(self, "critic_layer_norm", False):  # (class default False: an older pickle loads without it)
             eng.set_layer_norm(True)
+        drop = float(getattr(self, "critic_dropout", 0.0))
+        if drop > 0.0:  # (class default 0.0: an older pickle loads without it)
+            eng.set_critic_dropout(drop)
         return eng
+
+    def _set_dropout(self, critic_dropout):
+        """The TD3 / SAC constructors' keyword, checked as rle_set_critic_dropout checks it (before the engine
+        exists; 0.0 stays the class default: nothing new in the pickle)."""
+        p = float(critic_dropout)
+        if not 0.0 <= p < 1.0:
+            raise ValueError("critic_dropout must be in [0, 1) (0: no dropout)")
+        if p > 0.0:
+            self.critic_dropout = p
 
     def _set_layer_norm(self, critic_layer_norm):
         """The TD3 / SAC constructors' keyword (False stays the class default: nothing new in the pickle)."""
@@ -121,7 +145,8 @@ class EngineAgent(Agent, Sampler):
 
     def _host_critic(self, name):
         """A host-side rl.nn.MLPCritic with critic `name`'s current parameters (TD3 / SAC): the module the
-        reference keeps as agent.q1 / agent.q2, LayerNorm included, rebuilt from the device on each access."""
+        reference keeps as agent.q1 / agent.q2, LayerNorm and dropout included, rebuilt from the device on each
+        access (in train mode, as a new module is; .eval() gives what rle_eval computes)."""
         import torch
 
         from rl.nn.modules import MLPCritic
@@ -129,7 +154,8 @@ class EngineAgent(Agent, Sampler):
         fn = {"relu": "ReLU", "elu": "ELU", "identity": "Identity", "leaky_relu": "LeakyReLU", "silu": "SiLU",
               "gelu": "GELU"}[getattr(self, "acts", {}).get("act_critic", "relu")]
         sizes = self.shape.get("hidden_sizes", [self.hidden] * 2)
-        m = MLPCritic(self.state_dim, self.action_dim, sizes, action_fn=fn, layer_norm=self.critic_layer_norm)
+        m = MLPCritic(self.state_dim, self.action_dim, sizes, action_fn=fn, layer_norm=self.critic_layer_norm,
+                      dropout=getattr(self, "critic_dropout", 0.0))
         sd = {k: torch.from_numpy(np.array(v, np.float32)) for k, v in self.state_dict()[name].items()}
         m.load_state_dict(sd)
         return m

@@ -29,7 +29,12 @@ class SAC(EngineAgent):
     ``critic_layer_norm`` (keyword-only, default False) puts a parameter-free LayerNorm (``nn.LayerNorm(width,
     elementwise_affine=False)``, eps 1e-5) after every hidden Linear of q1, q2 and their targets, before the
     activation, in every pass of the device step (AWAC's forward-only passes included); the state_dict is
-    unchanged, and ``agent.q1`` / ``agent.q2`` give host copies (``rl.nn.MLPCritic``) that carry the norm."""
+    unchanged, and ``agent.q1`` / ``agent.q2`` give host copies (``rl.nn.MLPCritic``) that carry the norm.
+
+    ``critic_dropout`` (keyword-only, default 0.0 = off; needs ``critic_layer_norm=True``) makes every hidden block of
+    the critics ``Linear -> Dropout(p) -> LayerNorm -> activation``, the DroQ critic: inverted dropout as
+    ``torch.nn.Dropout(p)`` in train mode, active in every critic pass of the device step (target, online, policy),
+    drawn from a Philox stream of its own, and off in ``engine.eval_q`` (inference); the host copies carry it too."""
 
     ALG = "sac"
     ALGO = E.RLE_SAC
@@ -43,9 +48,11 @@ class SAC(EngineAgent):
                  max_grad_norm: float = float("inf"), make_nn=None, *, hidden: int = 256,
                  batch_size: int = 256, seed: int | None = None, device=None, offline: bool = False,
                  lmbda: float = 1.0, clip_grad_norm: float = float("inf"), critic_layer_norm: bool = False,
-                 **make_nn_kwargs) -> None:
+                 critic_dropout: float = 0.0, **make_nn_kwargs) -> None:
         # (parameter-free LayerNorm after every hidden Linear of the critics and their targets, in the device step)
         self._set_layer_norm(critic_layer_norm)
+        # (DroQ critics: dropout on every hidden Linear's output ahead of that LayerNorm, in the device step's passes)
+        self._set_dropout(critic_dropout)
         # (clip_grad_norm: global-norm clipping of the critics' and the policy's optimizer steps, applied in the
         # device step; the positional max_grad_norm stays what it is in the reference -- stored, never applied)
         self._set_clip(clip_grad_norm)

@@ -85,18 +85,47 @@ def _check_layer_norm(layer_norm) -> bool:
     return True
 
 
+_DROP_ONLY = ("dropout runs in the critics of TD3 / SAC only, inside their LayerNorm blocks, as "
+              "MLPCritic(layer_norm=True, dropout=p) with 0 <= p < 1: Linear -> Dropout(p) -> LayerNorm -> activation "
+              "in every hidden layer (dropout without LayerNorm is not run)")
+
+
+def _no_dropout(kind: str, dropout) -> None:
+    if dropout:
+        raise NotImplementedError(f"{kind}(dropout=...): {_DROP_ONLY}")
+
+
+def _check_dropout(dropout, layer_norm: bool) -> float:
+    """MLPCritic's dropout argument -> p (0.0: off).  A probability in [0, 1), or None / False; p > 0 needs
+    layer_norm.  Anything else is NotImplementedError (a probability outside [0, 1): ValueError)."""
+    if dropout is None or dropout is False:
+        return 0.0
+    if isinstance(dropout, bool) or not isinstance(dropout, (int, float)):
+        raise NotImplementedError(f"dropout={dropout!r}: {_DROP_ONLY}")
+    p = float(dropout)
+    if not 0.0 <= p < 1.0:  # (NaN fails too)
+        raise ValueError(f"dropout={dropout!r}: a probability in [0, 1)")
+    if p > 0.0 and not layer_norm:
+        raise NotImplementedError(f"dropout={p} without layer_norm: {_DROP_ONLY}")
+    return p
+
+
 class NormAct(nn.Module):
     """One hidden block's LayerNorm and activation as a single Sequential slot, so the Linear layers of a
     LayerNorm critic stay at indices 0, 2, 4, ... and its state_dict names are those of a plain one (the norm has
     no parameter and no buffer).  forward: act(layer_norm(z)) -- per row mu = mean(z), var = mean((z - mu)^2),
-    u = (z - mu) / sqrt(var + 1e-5), h = act(u)."""
+    u = (z - mu) / sqrt(var + 1e-5), h = act(u).  dropout = p > 0 (the DroQ block): F.dropout(z, p, self.training)
+    ahead of the norm -- inverted dropout in train(), nothing in eval()."""
 
-    def __init__(self, width: int, act: nn.Module):
+    def __init__(self, width: int, act: nn.Module, dropout: float = 0.0):
         super().__init__()
         self.norm = nn.LayerNorm(width, elementwise_affine=False)
         self.act = act
+        self.p = float(dropout)
 
     def forward(self, z):
+        if self.p > 0.0:
+            z = F.dropout(z, self.p, self.training)
         return self.act(self.norm(z))
 
 
@@ -104,8 +133,9 @@ class SALEEncoder(_Linears):
     """sale.py:16-55: zs = AvgL1Norm(zs3(elu(zs2(elu(zs1(s)))))), zsa = zsa3(elu(zsa2(elu(zsa1([zs, a])))))."""
 
     def __init__(self, state_dim: int, action_dim: int, zs_dim: int = 256, hdim: int = 256, activ=F.elu,
-                 layer_norm=False):
+                 layer_norm=False, dropout=0.0):
         _no_layer_norm("SALEEncoder", layer_norm)
+        _no_dropout("SALEEncoder", dropout)
         super().__init__(SALE_ENCODER, {"S": state_dim, "A": action_dim, "H": hdim, "Z": zs_dim})
         self.state_dim, self.action_dim, self.zs_dim, self.hdim, self.activ = state_dim, action_dim, zs_dim, hdim, activ
 
@@ -122,8 +152,9 @@ class SALEActor(_Linears):
     """sale.py:58-83: tanh(l3(relu(l2(relu(l1([AvgL1Norm(l0(s)), zs]))))))."""
 
     def __init__(self, state_dim: int, action_dim: int, zs_dim: int = 256, hdim: int = 256, activ=F.relu,
-                 layer_norm=False):
+                 layer_norm=False, dropout=0.0):
         _no_layer_norm("SALEActor", layer_norm)
+        _no_dropout("SALEActor", dropout)
         super().__init__(SALE_ACTOR, {"S": state_dim, "A": action_dim, "H": hdim, "Z": zs_dim})
         self.state_dim, self.action_dim, self.zs_dim, self.hdim, self.activ = state_dim, action_dim, zs_dim, hdim, activ
 
@@ -137,8 +168,9 @@ class SALECritic(_Linears):
     """sale.py:86-121: q3(elu(q2(elu(q1([AvgL1Norm(q01([s, a])), zsa, zs])))))."""
 
     def __init__(self, state_dim: int, action_dim: int, zs_dim: int = 256, hdim: int = 256, activ=F.elu,
-                 layer_norm=False):
+                 layer_norm=False, dropout=0.0):
         _no_layer_norm("SALECritic", layer_norm)  # (its q01 output already carries AvgL1Norm)
+        _no_dropout("SALECritic", dropout)
         super().__init__(SALE_CRITIC, {"S": state_dim, "A": action_dim, "H": hdim, "Z": zs_dim})
         self.state_dim, self.action_dim, self.zs_dim, self.hdim, self.activ = state_dim, action_dim, zs_dim, hdim, activ
 
@@ -147,11 +179,13 @@ class SALECritic(_Linears):
         return self.q3(self.activ(self.q2(self.activ(self.q1(h)))))
 
 
-def _mlp(fin: int, fout: int, hidden_sizes, action_fn="ReLU", init_weight=None, init_bias=None, layer_norm=False):
+def _mlp(fin: int, fout: int, hidden_sizes, action_fn="ReLU", init_weight=None, init_bias=None, layer_norm=False,
+         dropout=0.0):
     """make_mlp (mlp.py:10-35): Linear-act-...-Linear (indices 0, 2, 4, ...); weights by nn.init.<init_weight>
     (default xavier_normal_), biases by nn.init.<init_bias> (default zeros_).  Returns (Sequential, activation
     name).  action_fn=None is refused: make_mlp then pops the output Linear (mlp.py:34), not an activation.
-    layer_norm: every hidden block is Linear-NormAct (LayerNorm, then the activation, in the activation's slot)."""
+    layer_norm: every hidden block is Linear-NormAct (LayerNorm, then the activation, in the activation's slot);
+    dropout: the NormAct's own (ahead of its norm)."""
     if action_fn is None:
         raise NotImplementedError("make_mlp(action_fn=None) drops the output layer (mlp.py:34 pops the last Linear); "
                                   "use action_fn='Identity' for a net without activations")
@@ -165,7 +199,7 @@ def _mlp(fin: int, fout: int, hidden_sizes, action_fn="ReLU", init_weight=None, 
         lin = nn.Linear(dims[i], dims[i + 1])
         init_w(lin.weight.data)
         init_b(lin.bias.data)
-        mods += [lin, NormAct(dims[i + 1], act) if layer_norm else act]
+        mods += [lin, NormAct(dims[i + 1], act, dropout) if layer_norm else act]
     return nn.Sequential(*mods[:-1]), name
 
 
@@ -179,8 +213,10 @@ def _sizes(hidden_sizes):
 class MLPActor(nn.Module):
     """mlp.py:38-72: mean = mlp(s); SAC heads chunk it into (mean, log_std)."""
 
-    def __init__(self, state_dim: int, action_dim: int, hidden_sizes=256, layer_norm=False, **mlp_kwargs):
+    def __init__(self, state_dim: int, action_dim: int, hidden_sizes=256, layer_norm=False, dropout=0.0,
+                 **mlp_kwargs):
         _no_layer_norm("MLPActor", layer_norm)
+        _no_dropout("MLPActor", dropout)
         super().__init__()
         self.state_dim, self.action_dim, self.hidden_sizes = state_dim, action_dim, _sizes(hidden_sizes)
         self.mlp, self.act = _mlp(state_dim, action_dim, self.hidden_sizes, **mlp_kwargs)
@@ -194,28 +230,40 @@ class MLPActor(nn.Module):
 
 class MLPCritic(nn.Module):
     """mlp.py:75-104: q = mlp([s, a]).  layer_norm=True: parameter-free LayerNorm (eps 1e-5) after every hidden
-    Linear, before the activation (NormAct); the output layer is not normalised."""
+    Linear, before the activation (NormAct); the output layer is not normalised.  dropout=p with layer_norm=True: the
+    DroQ critic, Linear -> Dropout(p) -> LayerNorm -> activation in every hidden layer (active in train(), as in the
+    device step's passes; off in eval(), as in rle_eval)."""
 
-    def __init__(self, state_dim: int, action_dim: int, hidden_sizes=256, layer_norm=False, **mlp_kwargs):
+    def __init__(self, state_dim: int, action_dim: int, hidden_sizes=256, layer_norm=False, dropout=0.0,
+                 **mlp_kwargs):
         super().__init__()
         self.state_dim, self.action_dim, self.hidden_sizes = state_dim, action_dim, _sizes(hidden_sizes)
         self.layer_norm = _check_layer_norm(layer_norm)
+        self.dropout = _check_dropout(dropout, self.layer_norm)
         self.mlp, self.act = _mlp(state_dim + action_dim, 1, self.hidden_sizes, layer_norm=self.layer_norm,
-                                  **mlp_kwargs)
+                                  dropout=self.dropout, **mlp_kwargs)
 
     def estimate_q_value(self, state, action):
         return self.mlp(torch.cat([state, action], -1))
 
 
 def nets_from_make_nn(alg: str, make_nn, state_dim: int, action_dim: int, kwargs: dict):
+    """The first five values of nets_and_settings_from_make_nn (hidden width, net shape, state_dicts, activations,
+    LayerNorm): what callers from before the critics' dropout unpack."""
+    return nets_and_settings_from_make_nn(alg, make_nn, state_dim, action_dim, kwargs)[:5]
+
+
+def nets_and_settings_from_make_nn(alg: str, make_nn, state_dim: int, action_dim: int, kwargs: dict):
     """Call a reference-style make_nn hook (state_dim / action_dim passed as keywords, as
-    annotate_make_nn does) and return (hidden width, net shape, {net name: numpy state_dict}, activations) for
-    the engine.  Only this module's classes (the reference's default net types) are accepted, with
+    annotate_make_nn does) and return six values for the engine, in this order: the hidden width, the net shape,
+    {net name: numpy state_dict}, the activations, whether the critics carry LayerNorm, and the critics' dropout
+    probability.  Only this module's classes (the reference's default net types) are accepted, with
     one shape across the agent's nets: (hdim, zs_dim) of the SALE nets, hidden_sizes of the MLPs
     (the shape is {"zs_dim": ...} or {"hidden_sizes": [...]}, as rle_config takes them).  The
     activations are make_config's act_actor / act_critic / act_encoder (the names _act_name returns):
-    the SALE nets' `activ`, make_mlp's action_fn; the two critics must agree.  A fifth value tells whether the
-    critics carry LayerNorm (MLPCritic layer_norm; both critics must agree)."""
+    the SALE nets' `activ`, make_mlp's action_fn; the two critics must agree.  The fifth value is MLPCritic's
+    layer_norm (both critics must agree; False for TD7), the sixth MLPCritic's dropout (both critics must agree;
+    0.0: none)."""
     import numpy as np
 
     kw = dict(kwargs)
@@ -231,6 +279,7 @@ def nets_from_make_nn(alg: str, make_nn, state_dim: int, action_dim: int, kwargs
     nets = {}
     acts = {}
     lns = set()
+    drops = set()
     for name, kind, m in zip(names, kinds, out):
         if type(m) is not kind:
             raise NotImplementedError(f"make_nn returned {type(m).__name__} for {name}; the engine builds "
@@ -241,6 +290,7 @@ def nets_from_make_nn(alg: str, make_nn, state_dim: int, action_dim: int, kwargs
             raise NotImplementedError(f"one activation for both critics (got {acts[role]} and {act})")
         if isinstance(m, MLPCritic):
             lns.add(bool(getattr(m, "layer_norm", False)))
+            drops.add(float(getattr(m, "dropout", 0.0)))
         if isinstance(m, (SALEActor, SALECritic, SALEEncoder)):
             widths.add((m.hdim, m.zs_dim))
         else:
@@ -253,7 +303,9 @@ def nets_from_make_nn(alg: str, make_nn, state_dim: int, action_dim: int, kwargs
         raise NotImplementedError(f"one net shape across the agent's nets (got {sorted(widths)})")
     if len(lns) > 1:
         raise NotImplementedError("layer_norm must be the same for both critics (got one with and one without)")
+    if len(drops) > 1:
+        raise NotImplementedError(f"dropout must be the same for both critics (got {sorted(drops)})")
     w = widths.pop()
     if alg == "td7":
-        return w[0], {"zs_dim": w[1]}, nets, acts, False
-    return w[-1], {"hidden_sizes": list(w)}, nets, acts, bool(lns and lns.pop())
+        return w[0], {"zs_dim": w[1]}, nets, acts, False, 0.0
+    return w[-1], {"hidden_sizes": list(w)}, nets, acts, bool(lns and lns.pop()), (drops.pop() if drops else 0.0)
