@@ -25,6 +25,7 @@ extern "C" {
 #define RLE_SAC 2
 
 #define RLE_INFO_MAX 8
+#define RLE_MAX_N_STEP 8 /* rle_set_n_step / rle_replay_gather_nstep: the longest n-step return */
 
 #define RLE_OK 0
 #define RLE_EINVAL (-1)
@@ -224,6 +225,29 @@ int rle_replay_reset_max_priority(rle_replay* r);
 /* Gather rows (state, action, reward, next_state, notdone) for indices (lap.py:55-60). */
 int rle_replay_gather(rle_replay* r, int n, const long long* ind, float* state, float* action,
                       float* reward, float* next_state, float* notdone);
+/* The n-step law.  For a sampled slot i of a ring with capacity cap, `size` rows, write pointer ptr, n = n_step and
+ * gamma = discount, everything in fp32 with one rounding per product and per sum (no contraction):
+ *   cur = i; R = reward[cur]; g = 1.0f; hops = 1
+ *   while hops < n:
+ *       if notdone[cur] == 0: break                                  (terminated)
+ *       nxt = cur + 1; if nxt == cap: nxt = 0
+ *       if nxt >= size or nxt == ptr: break                          (cur is the newest row)
+ *       if bits(next_state[cur, :S]) != bits(state[nxt, :S]): break  (episode cut)
+ *       g = g * gamma; R = R + g * reward[nxt]; cur = nxt; hops += 1
+ *   out: state[i], action[i], R, next_state[cur], g * notdone[cur], hops
+ * Continuity comes from the data: row nxt continues row cur iff the S stored next_state words of cur equal the S
+ * state words of nxt as 32-bit patterns (so -0.0 != 0.0, and a NaN equals itself only with the same payload).  That
+ * catches time-limit truncation, resets, rle_replay_import seams and the write head, needs no column of its own (the
+ * ring, the packed row, snapshots and rle_replay_copy are unchanged), and survives rle_replay_normalize_states, which
+ * applies one fp32 expression to equal bits.  The one false positive: an episode whose reset state equals the previous
+ * row's next_state bit for bit is taken as its continuation.
+ * rle_replay_gather_nstep is the law's observable, as rle_replay_gather is the ring's: it runs the device function
+ * the step's sampler runs (on that sampler's kernel instance) for the given indices, each in 0 .. size-1, and returns
+ * the n-step host batch: state [n][S], action [n][A], reward [n] (R), next_state [n][S] (of the last hop), notdone [n]
+ * (gamma^(hops-1) * notdone of the last hop) and hops [n]; any output pointer may be NULL.  n_step 1 .. RLE_MAX_N_STEP
+ * (else RLE_EINVAL); n_step = 1 returns bit for bit what rle_replay_gather returns, and hops 1.  Syncs. */
+int rle_replay_gather_nstep(rle_replay* r, int n, const long long* ind, int n_step, float discount, float* state,
+                            float* action, float* reward, float* next_state, float* notdone, int* hops);
 /* Whole-replay state.  The reference's replays are NumPy arrays and Python scalars (lap.py:18-29,
  * simple.py:15-27), so pickle.dumps(replay) and copy.deepcopy(replay) work on them as they are, as
  * deepcopy(agent) does on the agent (run_w_checkpoint.py:72).  These entries give the HBM ring the same. */
@@ -325,6 +349,20 @@ int rle_get_critic_dropout(rle_engine* e, float* p);
  * (dropped) or s = 1 / (1 - p) (kept).  With p = 0 (dropout off) every element is kept and the output is all ones.
  * Syncs. */
 int rle_dropout_mask(rle_engine* e, long long step, int site, int rows, int width, float* out);
+/* n-step returns (TD3 / SAC): the step's sampler gathers, for every sampled slot, the n-step batch row of the law at
+ * rle_replay_gather_nstep with gamma = cfg.discount -- the n-step reward in the reward column, the last hop's
+ * next_state in the next-state rows, gamma^(hops-1) * notdone in the not-done column -- so the critic target
+ * y = r + gamma * notdone * Q'(s') becomes R + gamma^hops * notdone_last * Q'(s'_last), and every head, loss, LAP
+ * priority, offline mode, clip, LayerNorm and dropout path downstream runs unchanged, op for op.  Indices (sampled,
+ * LAP or taped) stay those of the first row; rle_last_indices and the priority update refer to it.
+ * n: 1 .. RLE_MAX_N_STEP (else RLE_EINVAL); 1 is off (default: today's programs on today's kernel instance; n > 1
+ * runs on a kernel instance of its own with the same level counts).  n > 1 on TD7 is RLE_EINVAL: its encoder learns
+ * the one-step model zsa(s, a) -> zs(s') from the same next-state rows.  Before the engine's first step (RLE_ESTATE
+ * after it).  Not part of the state: rle_copy_state / rle_copy_nets / rle_state_* work between engines whose n differ.
+ * With n > 1 the info row gains one column after the agent's own: replay/hops, the mean hops of the step's batch.
+ * Not run: n-step for TD7, an explicit episode-end column, per-row n, lambda-returns, n-step on a host batch. */
+int rle_set_n_step(rle_engine* e, int n);
+int rle_get_n_step(rle_engine* e, int* n);
 /* Bind the replay the step samples from (the replay_buffer arg of train_ops). */
 int rle_bind_replay(rle_engine* e, rle_replay* r);
 /* Parameter import/export in the reference's state_dict layout (Agent.load_state_dict,

@@ -194,6 +194,9 @@ struct Engine {
   int kernel_set() const {
     // (LayerNorm critics: OP_LN / OP_LN_BWD are KS_LN's alone; it holds KS_CLIP's code, so they compose with
     // clipping, every activation and both offline modes)
+    // (n-step returns: the sampler's multi-hop gather is KS_NSTEP's alone -- KS_DROP's code with it, so every
+    // setting below composes with it: LnArgs p == 0, no OP_LN and no OP_CLIP run on it as on their own instances)
+    if (n_step > 1) return KS_NSTEP;
     // (critic dropout: the row ops' dropout path is KS_DROP's alone -- KS_LN's code with it)
     if (ln_on() && drop_p > 0.f) return KS_DROP;
     if (ln_on()) return KS_LN;
@@ -227,6 +230,16 @@ struct Engine {
   float drop_p = 0.f;
   enum DropPass : int { DROP_TARGET = 0, DROP_ONLINE = 1, DROP_POLICY = 2, DROP_AWAC_DATA = 3, DROP_NONE = -1 };
   static int drop_site(int pass, int twin, int layer) { return (pass * 2 + twin) * 8 + layer; }
+  // n-step returns (rle_set_n_step): the sampler's gather walks up to n_step rows from the sampled slot and hands the
+  // step the n-step reward, the last hop's next_state and gamma^(hops-1) notdone in the batch's one-step places
+  // (ops.h SampleArgs), so no op downstream changes.  1: off.  TD3 / SAC.  hops: per batch set, the rows' hop
+  // counts for the info row's replay/hops (allocated by the setter: n_step == 1 allocates nothing).
+  int n_step = 1;
+  void ensure_hops() {
+    for (BatchSet& b : bsets)
+      if (!b.hops.p) b.hops = vec(B);
+    use_set(0);
+  }
   void resolve_plan() {
     if (plan.steps_per_graph < 0) plan.steps_per_graph = algo == RLE_TD3 ? 16 : algo == RLE_SAC ? 8 : 6;
     // (SAC's target critics' raw-head pre-GEMM consumers: 32 measured +1.0% over 64, 2 pairs)
@@ -354,12 +367,14 @@ struct Engine {
   // step buffers: two batch sets (the running step's and the prefetched next one)
   struct BatchSet {
     View ss, act_in, rw, nd, eps, eps2;
+    View hops;  // (n-step returns only: ensure_hops)
     long long* ind = nullptr;
     float* u_buf = nullptr;
     int ind_id = -1;
   };
   BatchSet bsets[2];
   View ss, act_in, rw, nd, eps, eps2;  // the set a program is being built on (use_set)
+  View hops;
   long long* ind = nullptr;
   float* u_buf = nullptr;
   double* bsum = nullptr;
@@ -371,6 +386,7 @@ struct Engine {
     nd = b.nd;
     eps = b.eps;
     eps2 = b.eps2;
+    hops = b.hops;
     ind = b.ind;
     u_buf = b.u_buf;
     ind_id = b.ind_id;
@@ -1947,7 +1963,9 @@ struct Engine {
       rd.push_back(pu->ind_id);
       rd.push_back(pu->p_id);
     }
-    pg.add(op, rd, {ss.id, act_in.id, rw.id, nd.id, ind_id});
+    std::vector<int> wr{ss.id, act_in.id, rw.id, nd.id, ind_id};
+    if (n_step > 1) wr.push_back(hops.id);  // (the gather writes the rows' hop counts)
+    pg.add(op, rd, wr);
     Op nz{};
     nz.kind = OP_NOISE;
     fill_sample_args(nz.sample, sac);
@@ -1993,6 +2011,13 @@ struct Engine {
     s.tape_eps = t_eps;
     s.tape_eps2 = t_eps2;
     s.tape_ind = t_ind;
+    if (n_step > 1) {  // (n_step == 1: the fields stay zero, the descriptor is the one it was)
+      REQUIRE(hops.p, "n-step returns: the hop buffers (rle_set_n_step allocates them)");
+      s.n_step = n_step;
+      s.gamma = cfg.discount;
+      s.ptr = rp.ptr_d;
+      s.hops_out = hops.p;
+    }
   }
 
   Op head_op(int mode, int rows) {
@@ -3275,6 +3300,12 @@ struct Engine {
       a.logpi_part = ploss_part;
       a.nlogpi = hw;
     }
+    if (n_step > 1) {  // one more column after the agent's own: replay/hops, the mean hops of this step's batch
+      REQUIRE(a.ninfo < kInfoMax, "n-step returns: the info row is full");
+      info_sum(a, a.ninfo, hops.p, Bv, 1, 1.f / (float)Bv);
+      ++a.ninfo;
+      rd.push_back(hops.id);
+    }
     std::vector<int> cn{CNT_ADAM_Q, 3, CNT_RNG, CNT_TAPE};
     if (policy) cn.push_back(CNT_ADAM_PI);
     add_step_end(pg, op, rd, cn);
@@ -4002,6 +4033,32 @@ int rle_dropout_mask(rle_engine* h, long long step, int site, int rows, int widt
     if (rc == hipSuccess) rc = hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost);
     (void)hipFree(d);
     HIPCHK(rc);
+  });
+}
+
+int rle_set_n_step(rle_engine* h, int n) {
+  return guard([&] {
+    REQUIRE(h, "set_n_step: null");
+    REQUIRE(n >= 1 && n <= RLE_MAX_N_STEP, "set_n_step: n must be in 1 .. RLE_MAX_N_STEP (1: off)");
+    Engine& e = drained(h);
+    REQUIRE(e.algo != RLE_TD7 || n == 1,
+            "set_n_step: TD3 / SAC only (TD7's encoder learns the one-step model zsa(s, a) -> zs(s') from the same "
+            "next-state rows)");
+    if (e.built)
+      throw Error{RLE_ESTATE, "set_n_step: the engine has already built its step programs (set it before the first "
+                              "step)"};
+    if (n > 1) {
+      HIPCHK(hipSetDevice(e.cfg.device));
+      e.ensure_hops();
+    }
+    e.n_step = n;
+  });
+}
+
+int rle_get_n_step(rle_engine* h, int* n) {
+  return guard([&] {
+    REQUIRE(h && n, "get_n_step: null");
+    *n = h->e->n_step;
   });
 }
 

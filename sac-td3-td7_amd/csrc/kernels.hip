@@ -2826,7 +2826,33 @@ __device__ __forceinline__ PendTab pend_prepare(const CAS SampleArgs& s, float* 
   return PendTab{wkey, wnext, wnew, wdel, bdel, bhead};
 }
 
-template <bool EXT>  // (EXT: the fused priority update, SampleArgs::pend_n)
+// n-step returns (SampleArgs n_step > 1, ops.h; the KS_NSTEP instance): whether the lane's column quad at c of
+// next_state row `a` and state row `b` differ in a column below S, as bit patterns (columns S .. Sp-1 are padding).
+__device__ __forceinline__ bool nstep_quad_differs(float4 a, float4 b, int c, int S) {
+  const unsigned dx = __float_as_uint(a.x) ^ __float_as_uint(b.x), dy = __float_as_uint(a.y) ^ __float_as_uint(b.y);
+  const unsigned dz = __float_as_uint(a.z) ^ __float_as_uint(b.z), dw = __float_as_uint(a.w) ^ __float_as_uint(b.w);
+  return (c < S && dx) || (c + 1 < S && dy) || (c + 2 < S && dz) || (c + 3 < S && dw);
+}
+// The law's products and sums, one float32 rounding each.  (This toolchain's __fmul_rn / __fadd_rn are a plain
+// x * y / x + y that hipcc's default, -ffp-contract=fast-honor-pragmas, fuses with a neighbour into one v_fma, an
+// ulp off the host's float32 chain; so the expressions stand under a contract(off) pragma of their own, which that
+// default honours.  An explicit -ffp-contract=fast in KFLAGS ignores the pragma and breaks the bit parity.)
+__device__ __forceinline__ float nstep_mul(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float nstep_madd(float acc, float g, float r) {
+#pragma clang fp contract(off)
+  const float p = g * r;
+  return acc + p;
+}
+__device__ __forceinline__ float readlane_f(float v, int l) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+
+// EXT: the fused priority update, SampleArgs::pend_n.  NSTEP: the multi-hop gather of n-step returns is compiled in
+// (the KS_NSTEP instance); without it the op is the one-step gather it was.
+template <bool EXT, bool NSTEP = false>
 __device__ __forceinline__ void op_sample_gather(const CAS SampleArgs& s, int t, float* smem, unsigned long long* tr) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int b = t * 4 + wave;  // query (wave-uniform)
@@ -2951,6 +2977,80 @@ __device__ __forceinline__ void op_sample_gather(const CAS SampleArgs& s, int t,
     rv = G(s.reward)[ind];
     dv = G(s.notdone)[ind];
   }
+  // n-step returns: the wave walks rows ind, ind + 1, ... (modulo cap) while each continues the one before (ops.h
+  // SampleArgs: not terminated, not past the newest row, next_state == state bit for bit).  Every row address is
+  // known from ind alone, so the loads of kHopGroup hops -- the first group's beside the loads above -- are issued
+  // before the first compare: one more round trip per kHopGroup hops, not per hop.  Lane l < n_step holds hop l's
+  // reward and notdone; R, g and the row in hand are wave-uniform.  v1 ends as next_state[cur], which all three
+  // store paths below take; `cur` itself serves the wide-row tail.
+  long long cur = ind;
+  if constexpr (NSTEP) {
+    const int n = s.n_step;  // (uniform)
+    if (n > 1) {
+      constexpr int kHopGroup = 3;
+      const long long cap = s.cap, wptr = sload(s.ptr);
+      auto row_of = [&](int h) {  // (h < n <= kMaxNStep <= cap is not required: the walk stops at ptr / size first)
+        long long r = ind + h;
+        while (r >= cap) r -= cap;
+        return r;
+      };
+      float hr = 0.f, hd = 0.f;  // lane h: reward and notdone of hop h's row (rows below cap: loads in bounds)
+      if (lane < n) {
+        const long long r = row_of(lane);
+        hr = G(s.reward)[r];
+        hd = G(s.notdone)[r];
+      }
+      float R = readlane_f(hr, 0), g = 1.0f, dn = readlane_f(hd, 0);
+      int hops = 1;
+      bool go = true;
+      for (int h0 = 1; h0 < n && go; h0 += kHopGroup) {
+        float4 cs[kHopGroup][2], cn[kHopGroup][2];
+#pragma unroll
+        for (int q = 0; q < kHopGroup; ++q) {
+          const long long r = row_of(h0 + q < n ? h0 + q : 0);
+#pragma unroll
+          for (int p = 0; p < 2; ++p) {
+            const int c = 4 * lane + 256 * p;
+            cs[q][p] = cn[q][p] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (c < s.Sp && h0 + q < n) {
+              cs[q][p] = ld4g(G(s.state) + (size_t)r * s.Sp + c);
+              cn[q][p] = ld4g(G(s.next_state) + (size_t)r * s.Sp + c);
+            }
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < kHopGroup; ++q) {
+          const int h = h0 + q;
+          if (h < n && go) {
+            const long long nxt = row_of(h);
+            bool differs = nstep_quad_differs(v1[0], cs[q][0], 4 * lane, s.S) ||
+                           nstep_quad_differs(v1[1], cs[q][1], 4 * lane + 256, s.S);
+            // (rows wider than the two passes: their remaining columns, a round trip per pass, as the stores' tail)
+            for (int c = 4 * lane + 512; c < s.Sp; c += 256)
+              differs = differs || nstep_quad_differs(ld4g(G(s.next_state) + (size_t)cur * s.Sp + c),
+                                                      ld4g(G(s.state) + (size_t)nxt * s.Sp + c), c, s.S);
+            const bool cont = dn != 0.f && nxt < size && nxt != wptr && __ballot(differs) == 0ull;
+            if (cont) {
+              g = nstep_mul(g, s.gamma);
+              R = nstep_madd(R, g, readlane_f(hr, h));
+              dn = readlane_f(hd, h);
+              v1[0] = cn[q][0];
+              v1[1] = cn[q][1];
+              cur = nxt;
+              ++hops;
+            } else {
+              go = false;
+            }
+          }
+        }
+      }
+      rv = R;
+      dv = nstep_mul(g, dn);
+      if (lane == 0 && s.hops_out) GW(s.hops_out)[b] = (float)hops;
+    } else if (lane == 0 && s.hops_out) {
+      GW(s.hops_out)[b] = 1.f;
+    }
+  }
   // (B % 4 == 0, every batch the engine draws: the workgroup's four rows b = 4 t .. 4 t + 3 are one
   // float4 of each T-image column -- mat_ld4's layout -- so they meet in LDS and each thread stores
   // whole float4s, instead of every wave storing its row as four scattered floats per column quad.
@@ -2976,7 +3076,7 @@ __device__ __forceinline__ void op_sample_gather(const CAS SampleArgs& s, int t,
   // (rows wider than the two passes above, state_dim 513..1024: their remaining columns, a round trip per pass)
   for (int c = 4 * lane + 512; c < s.Sp; c += 256) {
     mat_str4(s.ss, b, c, ld4g(G(s.state) + (size_t)ind * s.Sp + c));
-    mat_str4(s.ss, s.B + b, c, ld4g(G(s.next_state) + (size_t)ind * s.Sp + c));
+    mat_str4(s.ss, s.B + b, c, ld4g(G(s.next_state) + (size_t)(NSTEP ? cur : ind) * s.Sp + c));
   }
   if (4 * lane < s.Ap) {
     if (!quad) mat_str4(s.a, b, 4 * lane, va);
@@ -3589,7 +3689,7 @@ __global__ __launch_bounds__(kThreads, RLE_WAVES) void rle_level(unsigned e0, un
     RLE_OP(OP_GEMM, op_gemm<KS>(op.gemm, vid, t, smem, tr))
     RLE_OP(OP_NORMBWD, op_normbwd(op.nb, t))
     RLE_OP(OP_SAMPLE_REDUCE, op_sample_reduce(op.sample, t, smem))
-    RLE_OP(OP_SAMPLE_GATHER, op_sample_gather<ks_family(KS) == KS_EXT>(op.sample, t, smem, tr))
+    RLE_OP(OP_SAMPLE_GATHER, (op_sample_gather<ks_family(KS) == KS_EXT, ks_nstep(KS)>(op.sample, t, smem, tr)))
     RLE_OP(OP_HEAD, (op_head<ks_family(KS) == KS_EXT, ks_act_rt(KS)>(op.head, t, smem, tr)))
     RLE_OP(OP_PRIORITY, op_priority(op.prio, smem))
     RLE_OP(OP_SAC_ACTOR, op_sac_actor(op.sac, t))
@@ -3608,8 +3708,8 @@ __global__ __launch_bounds__(kThreads, RLE_WAVES) void rle_level(unsigned e0, un
            else if (ks_clip(KS) && vid == (OP_CLIP >> 4)) op_clip(op.clip, smem);
            // (OP_LN / OP_LN_BWD, LayerNorm critics: the KS_LN instance's, and KS_DROP's with the dropout path)
            else if constexpr (ks_ln(KS)) {
-             if (vid == (OP_LN >> 4)) (op_ln<false, KS == KS_DROP>)(op.ln, t);
-             else if (vid == (OP_LN_BWD >> 4)) (op_ln<true, KS == KS_DROP>)(op.ln, t);
+             if (vid == (OP_LN >> 4)) (op_ln<false, ks_drop(KS)>)(op.ln, t);
+             else if (vid == (OP_LN_BWD >> 4)) (op_ln<true, ks_drop(KS)>)(op.ln, t);
            })
 #undef RLE_OP
     default: break;
@@ -3620,8 +3720,8 @@ __global__ __launch_bounds__(kThreads, RLE_WAVES) void rle_level(unsigned e0, un
 // clip_level.hip compiles this file up to here (RLE_CLIP_TU) for the KS_CLIP instance alone: a code object of its
 // own, so this translation unit's -- every other instance and the stand-alone kernels below -- is the one it was
 // before clipped programs existed, down to the kernels' addresses.  ln_level.hip (RLE_LN_TU) does the same for KS_LN,
-// drop_level.hip (RLE_DROP_TU) for KS_DROP.
-#if !defined(RLE_CLIP_TU) && !defined(RLE_LN_TU) && !defined(RLE_DROP_TU)
+// drop_level.hip (RLE_DROP_TU) for KS_DROP, nstep_level.hip (RLE_NSTEP_TU) for KS_NSTEP.
+#if !defined(RLE_CLIP_TU) && !defined(RLE_LN_TU) && !defined(RLE_DROP_TU) && !defined(RLE_NSTEP_TU)
 
 // ---------------------------------------------------------------- B = 1 act chain (ops.h ActChainArgs)
 // Row block rb of layer L in registers: column block cb = wave + 4 i of the [16][K] strip, lane l
@@ -4106,7 +4206,10 @@ int trace_stride() { return kTraceStride; }
   X(KS_EXT, "_ZN3rle9rle_levelILb0ELi2EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd")  \
   X(KS_TD7W, "_ZN3rle9rle_levelILb0ELi3EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd") \
   X(KS_ACT, "_ZN3rle9rle_levelILb0ELi4EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd")
-// (KS_CLIP, KS_LN, KS_DROP: the last three KernelSets, instantiated in clip_level.hip, ln_level.hip and drop_level.hip)
+// (KS_CLIP, KS_LN, KS_DROP, KS_NSTEP: the last four KernelSets, instantiated in clip_level.hip, ln_level.hip,
+// drop_level.hip and nstep_level.hip)
+const void* nstep_level_fn(int traced);
+constexpr const char* kNstepLevelSymbol = "_ZN3rle9rle_levelILb0ELi8EEEvjjjjjjjjjjjjPKNS_2OpEPyS3_j.kd";
 const void* clip_level_fn(int traced);
 const void* ln_level_fn(int traced);
 const void* drop_level_fn(int traced);
@@ -4129,13 +4232,14 @@ constexpr bool level_rows_follow_enum() {
     if (kLevelRowKs[i] != i) return false;
   return true;
 }
-static_assert(sizeof(kLevelRowKs) == kLevelRows * sizeof(int) && level_rows_follow_enum() && KS_CLIP + 3 == KS_COUNT &&
-                  KS_LN + 2 == KS_COUNT && KS_DROP + 1 == KS_COUNT,
-              "RLE_LEVEL_INSTANCES: one row per KernelSet but the last three, in the enum's order");
+static_assert(sizeof(kLevelRowKs) == kLevelRows * sizeof(int) && level_rows_follow_enum() && KS_CLIP + 4 == KS_COUNT &&
+                  KS_LN + 3 == KS_COUNT && KS_DROP + 2 == KS_COUNT && KS_NSTEP + 1 == KS_COUNT,
+              "RLE_LEVEL_INSTANCES: one row per KernelSet but the last four, in the enum's order");
 static const void* level_fn(int traced, int ks) {
   return ks == KS_CLIP ? clip_level_fn(traced)
          : ks == KS_LN ? ln_level_fn(traced)
          : ks == KS_DROP ? drop_level_fn(traced)
+         : ks == KS_NSTEP ? nstep_level_fn(traced)
                          : kLevel.fn[traced][ks];
 }
 #undef RLE_ROW_KS
@@ -4158,7 +4262,11 @@ int level_capacity() {
 }
 
 const char* level_kernel_symbol(int ks) {
-  return ks == KS_CLIP ? kClipLevelSymbol : ks == KS_LN ? kLnLevelSymbol : ks == KS_DROP ? kDropLevelSymbol : kLevel.symbol[ks];
+  return ks == KS_CLIP ? kClipLevelSymbol
+         : ks == KS_LN ? kLnLevelSymbol
+         : ks == KS_DROP ? kDropLevelSymbol
+         : ks == KS_NSTEP ? kNstepLevelSymbol
+                          : kLevel.symbol[ks];
 }
 
 // Launches the instance the packet names with the packet's own argument bytes.
@@ -4239,6 +4347,12 @@ const void* clip_level_fn(int traced) {
 
 const void* ln_level_fn(int traced) {
   return traced ? (const void*)rle_level<true, KS_LN> : (const void*)rle_level<false, KS_LN>;
+}
+
+#elif defined(RLE_NSTEP_TU)
+
+const void* nstep_level_fn(int traced) {
+  return traced ? (const void*)rle_level<true, KS_NSTEP> : (const void*)rle_level<false, KS_NSTEP>;
 }
 
 #else  // RLE_DROP_TU

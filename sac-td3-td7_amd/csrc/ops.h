@@ -244,14 +244,23 @@ constexpr bool wide_variant(int mode, int epi, int pk) {
 // on -- again a set and (ln_level.hip) a code object of its own, so every other instance is the code it was, where
 // it was.  It holds KS_CLIP's code, so LayerNorm composes with every activation, both offline modes and clipping.
 enum KernelSet : int {
-  KS_TD7 = 0, KS_MLP = 1, KS_EXT = 2, KS_TD7W = 3, KS_ACT = 4, KS_CLIP = 5, KS_LN = 6, KS_DROP = 7, KS_COUNT = 8
+  KS_TD7 = 0, KS_MLP = 1, KS_EXT = 2, KS_TD7W = 3, KS_ACT = 4, KS_CLIP = 5, KS_LN = 6, KS_DROP = 7, KS_NSTEP = 8,
+  KS_COUNT = 9
 };
 // KS_DROP: KS_LN's code with the row ops' critic-dropout path compiled in (LnArgs p > 0), for engines with
 // rle_set_critic_dropout on -- once more a set and (drop_level.hip) a code object of its own: KS_LN compiles the
 // row ops without that path, so ln_level.hip's code object is the one it was before critic dropout existed.
-constexpr bool ks_ln(int ks) { return ks == KS_LN || ks == KS_DROP; }
+// KS_NSTEP: KS_DROP's code with the sampler's multi-hop gather compiled in (SampleArgs n_step > 1), for engines with
+// rle_set_n_step on -- the next link of the chain, a set and (nstep_level.hip) a code object of its own: every other
+// instance compiles the one-step gather, so their code objects are the ones they were before n-step returns existed.
+// It holds every earlier link's code, so n-step composes with clipping, LayerNorm, dropout, every activation and
+// both offline modes; LnArgs p == 0 and a program without OP_CLIP / OP_LN run on it as they do on their own instances.
+constexpr bool ks_nstep(int ks) { return ks == KS_NSTEP; }
+// the instances whose row ops compile the critic-dropout path
+constexpr bool ks_drop(int ks) { return ks == KS_DROP || ks == KS_NSTEP; }
+constexpr bool ks_ln(int ks) { return ks == KS_LN || ks_drop(ks); }
 // the instances that hold the clipped programs' code (EPI_GSQ, the sets-4 variants, OP_CLIP)
-constexpr bool ks_clip(int ks) { return ks == KS_CLIP || ks == KS_LN || ks == KS_DROP; }
+constexpr bool ks_clip(int ks) { return ks == KS_CLIP || ks_ln(ks); }
 // the agent family whose variants (RLE_GEMM_VARIANTS sets bit) and ops an instance compiles
 constexpr int ks_family(int ks) { return ks == KS_TD7W ? KS_TD7 : ks == KS_ACT || ks_clip(ks) ? KS_EXT : ks; }
 // the instances that dispatch an ELU id a second time on the op's activation (kActRt: LeakyReLU / SiLU / GELU)
@@ -511,7 +520,21 @@ struct SampleArgs {
   // OP_PRIORITY runs after this op): pend_p[b] for row pend_ind[b], b < pend_n, last duplicate
   // wins (lap.py:66-69); the search reads the sums and priorities as that update leaves them
   const long long* pend_ind; const float* pend_p; int pend_n;
+  // n-step returns (rle_set_n_step; the KS_NSTEP instance alone reads these -- n_step <= 1 or any other instance:
+  // the one-step gather).  From the sampled slot i the wave walks rows i, i+1, ... (modulo cap), at most n_step of
+  // them, everything in fp32 with one rounding per product and per sum (rle.h "n-step law"):
+  //   cur = i; R = reward[cur]; g = 1; hops = 1
+  //   while hops < n_step:
+  //     notdone[cur] == 0 -> stop (terminated);  nxt = cur + 1 (cap -> 0);  nxt >= size or nxt == ptr -> stop (cur is
+  //     the newest row);  the S next_state words of cur != the S state words of nxt, as bit patterns -> stop (cut)
+  //     g = g * gamma;  R = R + g * reward[nxt];  cur = nxt;  hops += 1
+  // and the batch row gets state[i], action[i], r = R, next_state[cur], nd = g * notdone[cur], hops_out = hops.
+  int n_step;                        // 1 .. kMaxNStep (0 as 1)
+  float gamma;                       // the discount of the law
+  const long long* ptr;              // device copy of the replay's write pointer (Replay::ptr_d)
+  float* hops_out;                   // [B] the hops of each row, as a float (the info row's replay/hops sums it)
 };
+constexpr int kMaxNStep = 8;  // (RLE_MAX_N_STEP)
 
 struct PriorityArgs {
   float* priority; const long long* ind; const float* p; int B;

@@ -651,6 +651,10 @@ void OpAccesses::op_accesses(const Op& op, std::vector<Access>& v) const {
       acc_whole(v, s.nd, 1, "batch nd");
       acc_whole(v, s.ind, 1, "batch ind");
       acc_whole(v, s.u_out, 1, "batch u");
+      if (s.n_step > 1) {  // (n-step returns: the write pointer beside the size, and the rows' hop counts)
+        acc_bytes(v, s.ptr, 8, 0, "replay ptr");
+        acc_whole(v, s.hops_out, 1, "batch hops");
+      }
       break;
     }
     case OP_HEAD: {
@@ -923,6 +927,11 @@ LevelTraffic level_traffic(const std::vector<Op>& ops, const float* P, size_t nP
       t.other += (double)s.nq * (2.0 * s.Sp + s.Ap + 2) * 4 + (s.lap ? s.nq * (64.0 * 8 + 64 * 4) + s.nblk * 8.0 : 0);
       t.act_w += (double)s.B * ((s.ss.n != nullptr) + (s.ss.t != nullptr)) * 2 * s.Sp * 4 +
                  (double)s.B * ((s.a.n != nullptr) + (s.a.t != nullptr)) * s.Ap * 4 + s.B * 20.0;
+      if (s.n_step > 1) {  // n-step returns: a state and a next_state row, reward and notdone per further hop (the
+                           // walk's upper bound: every hop's loads are issued), and the hop count per row
+        t.other += (double)s.nq * (s.n_step - 1) * (2.0 * s.Sp + 2) * 4;
+        t.act_w += s.B * 4.0;
+      }
       continue;
     }
     if (op.kind == OP_PRIORITY) {  // the scattered rows (a 64-B line each) and their two sums

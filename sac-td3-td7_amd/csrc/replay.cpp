@@ -25,6 +25,11 @@ void Replay::remove_user(Engine* e) {
       break;
     }
 }
+void Replay::push_cursor() {
+  // (size_d and ptr_d are one allocation, {size, ptr}: one copy)
+  cursor_host[0] = size, cursor_host[1] = ptr;
+  HIPCHK(hipMemcpyAsync(size_d, cursor_host, sizeof cursor_host, hipMemcpyHostToDevice, stream));
+}
 void Replay::io_init() {
   if (io_stream) return;
   const size_t n = (size_t)std::min(kIoRows, cap) * row_floats();  // (a chunk never has more rows than the ring)
@@ -101,7 +106,8 @@ int rle_replay_create(int device, long long capacity, int state_dim, int action_
       r.reward = r.mem.make<float>(capacity);
       r.notdone = r.mem.make<float>(capacity);
       r.priority = r.mem.make<float>(capacity);
-      r.size_d = r.mem.make<long long>(1);
+      r.size_d = r.mem.make<long long>(2);  // {size, ptr} (zero from the allocation: an empty ring)
+      r.ptr_d = r.size_d + 1;
       r.maxp_d = r.mem.make<float>(1);
       const float one = 1.f;  // lap.py:29 max_priority = 1
       HIPCHK(hipMemcpy(r.maxp_d, &one, 4, hipMemcpyHostToDevice));
@@ -183,7 +189,7 @@ int rle_replay_append(rle_replay* h, const float* state, const float* action, co
       r.ptr = (r.ptr + c) % r.cap;
       r.size = std::min(r.size + c, r.cap);
       ++r.version;
-      HIPCHK(hipMemcpyAsync(r.size_d, &r.size, sizeof(long long), hipMemcpyHostToDevice, r.stream));
+      r.push_cursor();
       HIPCHK(hipStreamSynchronize(r.stream));
       done += c;
     }
@@ -217,7 +223,7 @@ int rle_replay_fill_random(rle_replay* h, long long count, unsigned long long se
     r.size = std::max(r.size, count);
     r.ptr = count % r.cap;
     ++r.version;
-    HIPCHK(hipMemcpyAsync(r.size_d, &r.size, sizeof(long long), hipMemcpyHostToDevice, r.stream));
+    r.push_cursor();
     HIPCHK(hipStreamSynchronize(r.stream));
     if (r.lap) recompute_bsum(r);
   });
@@ -245,7 +251,7 @@ int rle_replay_set_priority(rle_replay* h, const float* p, long long n, float ma
 }
 
 // Runs a small op program eagerly on the replay's stream (test hooks).
-static void run_eager(Replay& r, std::vector<std::vector<rle::Op>> levels) {
+static void run_eager(Replay& r, std::vector<std::vector<rle::Op>> levels, int ks = rle::KS_EXT) {
   for (size_t l = 0; l < levels.size(); ++l) {
     auto& lv = levels[l];
     int wg = 0;
@@ -255,7 +261,7 @@ static void run_eager(Replay& r, std::vector<std::vector<rle::Op>> levels) {
     }
     rle::Op* d = r.scratch.get<rle::Op>("ops" + std::to_string(l), lv.size());
     HIPCHK(hipMemcpy(d, lv.data(), lv.size() * sizeof(rle::Op), hipMemcpyHostToDevice));
-    HIPCHK(rle::launch_level(d, lv.data(), (int)lv.size(), wg, r.stream));
+    HIPCHK(rle::launch_level(d, lv.data(), (int)lv.size(), wg, r.stream, nullptr, nullptr, 0, ks));
   }
   HIPCHK(hipStreamSynchronize(r.stream));
 }
@@ -424,6 +430,107 @@ int rle_replay_gather(rle_replay* h, int n, const long long* ind, float* state, 
   });
 }
 
+// The n-step host batch of rle.h's law: the sampler's own gather (OP_SAMPLE_GATHER on the KS_NSTEP instance, the
+// op the step runs) with the caller's indices as its index tape, into N and T batch images as a step's are, read
+// back and unpacked here.  The T images pass through the op's LDS-staged stores where the row shape takes them, the
+// N images through its direct ones: both must hold the same rows.
+int rle_replay_gather_nstep(rle_replay* h, int n, const long long* ind, int n_step, float discount, float* state,
+                            float* action, float* reward, float* next_state, float* notdone, int* hops) {
+  return guard([&] {
+    REQUIRE(h && n >= 0 && (ind || n == 0), "gather_nstep: bad args");
+    REQUIRE(n_step >= 1 && n_step <= rle::kMaxNStep, "gather_nstep: n_step outside 1 .. RLE_MAX_N_STEP");
+    REQUIRE(std::isfinite(discount), "gather_nstep: discount must be finite");
+    Replay& r = h->r;
+    REQUIRE(n == 0 || r.size > 0, "gather_nstep: empty replay");
+    for (int i = 0; i < n; ++i) REQUIRE(ind[i] >= 0 && ind[i] < r.size, "gather_nstep: index outside 0 .. size-1");
+    if (n == 0) return;
+    HIPCHK(hipSetDevice(r.device));
+    r.wait_users();
+    rle::Scratch& tmp = r.scratch;
+    constexpr int kChunk = 1024;  // queries per launch (a step's largest batch)
+    const int Bmax = rle::r16(std::min(n, kChunk));
+    auto img = [&](const char* name, int rows, int cols) {  // N + T images of [rows][cols], rows % 16 == 0
+      rle::Mat m{};
+      m.rbs = rows / 16;
+      m.cbn = cols / 16;
+      m.n = tmp.get<float>(std::string(name) + "_n", (size_t)rows * cols);
+      m.t = tmp.get<float>(std::string(name) + "_t", (size_t)rows * cols);
+      return m;
+    };
+    const rle::Mat ss_all = img("ns_ss", 2 * Bmax, r.Sp), a_all = img("ns_a", Bmax, r.Ap);
+    float* d_r = tmp.get<float>("ns_r", Bmax);
+    float* d_nd = tmp.get<float>("ns_nd", Bmax);
+    float* d_hops = tmp.get<float>("ns_hops", Bmax);
+    long long* d_ind = tmp.get<long long>("ns_ind", Bmax);
+    long long* d_tape = tmp.get<long long>("ns_tape", Bmax);
+    long long* cnt = tmp.get<long long>("ns_ctl", 3);  // [0] rng step, [1] tape position, [2] tape mode
+    const long long ctl[3] = {0, 0, rle::kTapeInd};
+    HIPCHK(hipMemcpyAsync(cnt, ctl, sizeof ctl, hipMemcpyHostToDevice, r.stream));
+    auto n_at = [](int cbn, int row, int c) {
+      return ((size_t)(row >> 4) * cbn + (c >> 4)) * 256 + ((c >> 2) & 3) * 64 + (row & 15) * 4 + (c & 3);
+    };
+    auto t_at = [](int rbs, int row, int c) {
+      return ((size_t)(c >> 4) * rbs + (row >> 4)) * 256 + ((row >> 2) & 3) * 64 + (c & 15) * 4 + (row & 3);
+    };
+    std::vector<float> hn, ht, hv((size_t)Bmax * 3);
+    for (int row0 = 0; row0 < n; row0 += kChunk) {
+      const int c = std::min(kChunk, n - row0), B = rle::r16(c);
+      rle::SampleArgs s{};
+      s.state = r.state, s.next_state = r.next_state, s.action = r.action;
+      s.reward = r.reward, s.notdone = r.notdone, s.priority = r.priority;
+      s.S = r.S, s.Sp = r.Sp, s.A = r.A, s.Ap = r.Ap;
+      s.size = r.size_d;
+      s.cap = r.cap;
+      s.lap = 0;
+      s.B = B;
+      s.nq = c;
+      s.ss = ss_all;
+      s.ss.rbs = 2 * B / 16;
+      s.a = a_all;
+      s.a.rbs = B / 16;
+      s.r = d_r, s.nd = d_nd, s.ind = d_ind;
+      s.ctrl_rng = cnt;
+      s.tape_pos = cnt + 1;
+      s.tape_mode = (const int*)(cnt + 2);
+      s.tape_ind = d_tape;
+      s.n_step = n_step;
+      s.gamma = discount;
+      s.ptr = r.ptr_d;
+      s.hops_out = d_hops;
+      HIPCHK(hipMemcpyAsync(d_tape, ind + row0, (size_t)c * sizeof(long long), hipMemcpyHostToDevice, r.stream));
+      rle::Op op{};
+      op.kind = rle::OP_SAMPLE_GATHER;
+      op.sample = s;
+      op.wg_count = rle::cdiv(c, 4);
+      run_eager(r, {{op}}, rle::KS_NSTEP);
+      auto unpack = [&](const rle::Mat& m, int rows, int cols, int src_row0, int width, float* out) {
+        if (!out) return;
+        hn.resize((size_t)rows * cols), ht.resize((size_t)rows * cols);
+        HIPCHK(hipMemcpy(hn.data(), m.n, hn.size() * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(ht.data(), m.t, ht.size() * 4, hipMemcpyDeviceToHost));
+        for (int b = 0; b < c; ++b)
+          for (int j = 0; j < width; ++j) {
+            const float vn = hn[n_at(m.cbn, src_row0 + b, j)], vt = ht[t_at(m.rbs, src_row0 + b, j)];
+            if (std::memcmp(&vn, &vt, 4) != 0)
+              throw Error{RLE_EHIP, "gather_nstep: the batch's N and T images differ"};
+            out[((size_t)row0 + b) * width + j] = vt;
+          }
+      };
+      unpack(s.ss, 2 * B, r.Sp, 0, r.S, state);
+      unpack(s.ss, 2 * B, r.Sp, B, r.S, next_state);
+      unpack(s.a, B, r.Ap, 0, r.A, action);
+      HIPCHK(hipMemcpy(hv.data(), d_r, (size_t)c * 4, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(hv.data() + Bmax, d_nd, (size_t)c * 4, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(hv.data() + 2 * Bmax, d_hops, (size_t)c * 4, hipMemcpyDeviceToHost));
+      for (int b = 0; b < c; ++b) {
+        if (reward) reward[row0 + b] = hv[b];
+        if (notdone) notdone[row0 + b] = hv[Bmax + b];
+        if (hops) hops[row0 + b] = (int)hv[2 * Bmax + b];
+      }
+    }
+  });
+}
+
 int rle_replay_io_rows(void) { return (int)Replay::kIoRows; }
 
 int rle_replay_export(rle_replay* h, long long first, long long count, float* state, float* action, float* reward,
@@ -508,7 +615,7 @@ int rle_replay_set_state(rle_replay* h, long long ptr, long long size, float max
     r.wait_users();
     r.ptr = ptr;
     r.size = size;
-    HIPCHK(hipMemcpyAsync(r.size_d, &r.size, sizeof(long long), hipMemcpyHostToDevice, r.stream));
+    r.push_cursor();
     HIPCHK(hipMemcpyAsync(r.maxp_d, &max_priority, sizeof(float), hipMemcpyHostToDevice, r.stream));
     HIPCHK(hipStreamSynchronize(r.stream));
     if (r.lap) recompute_bsum(r);  // (rows at or past size count as 0)
@@ -617,10 +724,10 @@ int rle_replay_copy(rle_replay* hd, rle_replay* hs) {
     cp(d.bsum, s.bsum, (size_t)s.nblk * sizeof(double));
     cp(d.ssum, s.ssum, (size_t)s.nblk * 64 * sizeof(double));
     cp(d.maxp_d, s.maxp_d, sizeof(float));
-    cp(d.size_d, s.size_d, sizeof(long long));
-    HIPCHK(hipStreamSynchronize(d.stream));
     d.ptr = s.ptr;
     d.size = s.size;
+    d.push_cursor();  // (from the host's values: the source's device copies are these same two)
+    HIPCHK(hipStreamSynchronize(d.stream));
     ++d.version;
   });
 }

@@ -20,6 +20,9 @@ struct Replay {
   long long ptr = 0, size = 0;
   float *state, *next_state, *action, *reward, *notdone, *priority;
   long long* size_d;
+  // device copy of ptr, next to size_d and kept current wherever size_d is (push_cursor): the n-step gather stops
+  // a walk at the write head (ops.h SampleArgs::ptr)
+  long long* ptr_d;
   float* maxp_d;
   double* bsum;
   double* ssum;  // LAP sub-block sums (64 priorities each), nblk * 64
@@ -52,6 +55,9 @@ struct Replay {
   size_t gather_host_floats = 0;
   size_t row_floats() const { return 2 * (size_t)S + A + 3; }
   void io_init();
+  // The device copies of size and ptr from the host's, on `stream` (the caller synchronises).
+  long long cursor_host[2] = {0, 0};  // the copy's source (a member: it outlives the asynchronous copy)
+  void push_cursor();
   ReplayPackArgs pack_args() const {
     ReplayPackArgs a{};
     a.state = state, a.next_state = next_state, a.action = action;

@@ -17,6 +17,7 @@ import numpy as np
 RLE_TD7, RLE_TD3, RLE_SAC = 0, 1, 2
 RLE_EVAL_Q, RLE_EVAL_ZS, RLE_EVAL_ZSA = 0, 1, 2
 INFO_MAX = 8
+MAX_N_STEP = 8  # RLE_MAX_N_STEP
 REPLAY_IO_ROWS = 8192  # rle_replay_io_rows(): rows per staging chunk of replay export / import
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -164,6 +165,8 @@ SIGNATURES = {
     "rle_replay_update_priority": (_int, [_vp, _int, _i64p, _f32p]),
     "rle_replay_reset_max_priority": (_int, [_vp]),
     "rle_replay_gather": (_int, [_vp, _int, _i64p, _f32p, _f32p, _f32p, _f32p, _f32p]),
+    "rle_replay_gather_nstep": (_int, [_vp, _int, _i64p, _int, ctypes.c_float, _f32p, _f32p, _f32p, _f32p, _f32p,
+                                       ctypes.POINTER(ctypes.c_int)]),
     "rle_replay_io_rows": (_int, []),
     "rle_replay_export": (_int, [_vp, _ll, _ll, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]),
     "rle_replay_import": (_int, [_vp, _ll, _ll, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]),
@@ -185,6 +188,8 @@ SIGNATURES = {
     "rle_set_critic_dropout": (_int, [_vp, ctypes.c_float]),
     "rle_get_critic_dropout": (_int, [_vp, _f32p]),
     "rle_dropout_mask": (_int, [_vp, _ll, _int, _int, _int, _f32p]),
+    "rle_set_n_step": (_int, [_vp, _int]),
+    "rle_get_n_step": (_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
     "rle_bind_replay": (_int, [_vp, _vp]),
     "rle_param_numel": (_int, [_vp, _cs, _cs, _i64p]),
     "rle_get_param": (_int, [_vp, _cs, _cs, _f32p, _ll]),
@@ -337,6 +342,23 @@ class Replay:
         _check(lib().rle_replay_gather(self.h, n, _ip(ind), _fp(s), _fp(a), _fp(r), _fp(s2), _fp(d)))
         return s, a, r, s2, d
 
+    def gather_nstep(self, ind, n_step, discount):
+        """The n-step batch of rle.h's law for slots `ind` (each < size), computed by the step's own sampler
+        (rle_replay_gather_nstep): (state, action, R, next_state of the last hop, gamma^(hops-1) * notdone of the
+        last hop, hops).  n_step = 1 is gather() and hops 1."""
+        ind = np.ascontiguousarray(ind, np.int64)
+        n = ind.size
+        s = np.empty((n, self.S), np.float32)
+        a = np.empty((n, self.A), np.float32)
+        r = np.empty(n, np.float32)
+        s2 = np.empty((n, self.S), np.float32)
+        d = np.empty(n, np.float32)
+        hops = np.empty(n, np.int32)
+        _check(lib().rle_replay_gather_nstep(self.h, n, _ip(ind), int(n_step), ctypes.c_float(discount), _fp(s),
+                                             _fp(a), _fp(r), _fp(s2), _fp(d),
+                                             hops.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return s, a, r, s2, d, hops
+
     def export_rows(self, first, count, priority=False):
         """Slots first .. first+count-1 as unpadded fp32 arrays (rle_replay_export):
         (state, action, reward, next_state, notdone), plus priority when asked (LAP replays)."""
@@ -434,6 +456,18 @@ class Engine:
         v = ctypes.c_int(0)
         _check(lib().rle_get_layer_norm(self.h, ctypes.byref(v)))
         return bool(v.value)
+
+    def set_n_step(self, n: int):
+        """n-step returns (rle_set_n_step): the step's sampler gathers the n-step reward, the last hop's next_state
+        and gamma^(hops-1) * notdone for every sampled slot.  1 <= n <= MAX_N_STEP, 1 off.  TD3 / SAC.  Before the
+        first step."""
+        _check(lib().rle_set_n_step(self.h, ctypes.c_int(int(n))))
+
+    def n_step(self) -> int:
+        """The engine's n of its n-step returns (rle_get_n_step; 1: off)."""
+        v = ctypes.c_int(0)
+        _check(lib().rle_get_n_step(self.h, ctypes.byref(v)))
+        return int(v.value)
 
     def set_critic_dropout(self, p: float):
         """Inverted dropout (torch.nn.Dropout(p) in train mode) on every hidden Linear's output of the critics and
@@ -712,6 +746,21 @@ class Engine:
 
     def synchronize(self):
         _check(lib().rle_synchronize(self.h))
+
+
+def check_n_step(algo, n_step) -> int:
+    """The n of n-step returns as rle_set_n_step checks it, before an engine exists: an int in 1 .. MAX_N_STEP
+    (1: off), and 1 on TD7, whose encoder learns the one-step model zsa(s, a) -> zs(s') from the same next-state
+    rows.  Returns it as an int; anything else is a ValueError."""
+    if isinstance(n_step, bool) or int(n_step) != n_step:
+        raise ValueError(f"n_step {n_step!r}: an integer in 1 .. {MAX_N_STEP}")
+    n = int(n_step)
+    if not 1 <= n <= MAX_N_STEP:
+        raise ValueError(f"n_step {n}: must be in 1 .. {MAX_N_STEP} (1: one-step targets)")
+    if n > 1 and algo == RLE_TD7:
+        raise ValueError("n_step > 1 is TD3 / SAC only: TD7's encoder learns the one-step model zsa(s, a) -> zs(s') "
+                         "from the same next-state rows")
+    return n
 
 
 def make_config(algo, state_dim, action_dim, hidden, batch, use_lap=False, discount=0.99,

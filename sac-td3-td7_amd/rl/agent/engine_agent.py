@@ -41,6 +41,8 @@ class EngineAgent(Agent, Sampler):
     # dropout probability on every hidden Linear's output of the critics, ahead of the LayerNorm
     # (rle_set_critic_dropout; TD3 / SAC, needs critic_layer_norm); 0.0: off
     critic_dropout: float = 0.0
+    # n of the n-step returns the device sampler gathers (rle_set_n_step; TD3 / SAC); 1: one-step targets
+    n_step: int = 1
 
     def _setup(self, env_id, *, hidden, batch_size, seed, device, make_nn, make_nn_kwargs, cfg):
         custom = None
@@ -127,7 +129,21 @@ class EngineAgent(Agent, Sampler):
         drop = float(getattr(self, "critic_dropout", 0.0))
         if drop > 0.0:  # (class default 0.0: an older pickle loads without it)
             eng.set_critic_dropout(drop)
+        n = int(getattr(self, "n_step", 1))
+        if n > 1:  # (class default 1: an older pickle loads without it)
+            eng.set_n_step(n)
         return eng
+
+    def _set_n_step(self, n_step):
+        """The constructors' keyword, checked as rle_set_n_step checks it (before the engine exists; 1 stays the
+        class default: nothing new in the pickle)."""
+        n = E.check_n_step(self.ALGO, n_step)
+        if n > 1:
+            self.n_step = n
+
+    def _with_hops(self, keys):
+        """The info row's keys with the n-step column after the agent's own (TD3 / SAC _info_keys)."""
+        return keys + ("replay/hops",) if getattr(self, "n_step", 1) > 1 else keys
 
     def _set_dropout(self, critic_dropout):
         """The TD3 / SAC constructors' keyword, checked as rle_set_critic_dropout checks it (before the engine
@@ -378,6 +394,9 @@ class EngineAgent(Agent, Sampler):
         and a LAP replay_buffer gets the new priorities through its own update_priority (and its
         reset_max_priority at TD7 hard updates), as td7.py:236-240, 325-331 would call them."""
 
+        if getattr(self, "n_step", 1) > 1:
+            raise ValueError("train_ops on a host BATCH dict with n_step > 1: its B-row scratch ring has no episode "
+                             "order (train from a device replay's sample(), or train_n)")
         missing = [k for k in ("state", "action", "reward", "next_state", "done") if k not in batch]
         if missing:
             raise ValueError(f"BATCH (annotation.py:23-30) without {missing}")

@@ -34,7 +34,13 @@ class SAC(EngineAgent):
     ``critic_dropout`` (keyword-only, default 0.0 = off; needs ``critic_layer_norm=True``) makes every hidden block of
     the critics ``Linear -> Dropout(p) -> LayerNorm -> activation``, the DroQ critic: inverted dropout as
     ``torch.nn.Dropout(p)`` in train mode, active in every critic pass of the device step (target, online, policy),
-    drawn from a Philox stream of its own, and off in ``engine.eval_q`` (inference); the host copies carry it too."""
+    drawn from a Philox stream of its own, and off in ``engine.eval_q`` (inference); the host copies carry it too.
+
+    ``n_step`` (keyword-only, default 1 = one-step targets, at most 8) trains on n-step returns: the device sampler
+    walks up to ``n_step`` consecutive rows of the sampled slot's episode (continuity is read from the data:
+    ``next_state[i] == state[i + 1]`` bit for bit) and the critic target becomes ``R_n + gamma^hops * notdone *
+    (min Q' - alpha logpi)(s_last')``; the info dict gains ``replay/hops``, the batch's mean hops.
+    ``replay.sample(B, n_step=n, discount=gamma)`` returns the same rows on the host; a host BATCH dict is refused."""
 
     ALG = "sac"
     ALGO = E.RLE_SAC
@@ -48,7 +54,9 @@ class SAC(EngineAgent):
                  max_grad_norm: float = float("inf"), make_nn=None, *, hidden: int = 256,
                  batch_size: int = 256, seed: int | None = None, device=None, offline: bool = False,
                  lmbda: float = 1.0, clip_grad_norm: float = float("inf"), critic_layer_norm: bool = False,
-                 critic_dropout: float = 0.0, **make_nn_kwargs) -> None:
+                 critic_dropout: float = 0.0, n_step: int = 1, **make_nn_kwargs) -> None:
+        # (n-step returns: the device sampler hands the step the n-step reward, next state and discount factor)
+        self._set_n_step(n_step)
         # (parameter-free LayerNorm after every hidden Linear of the critics and their targets, in the device step)
         self._set_layer_norm(critic_layer_norm)
         # (DroQ critics: dropout on every hidden Linear's output ahead of that LayerNorm, in the device step's passes)
@@ -92,10 +100,12 @@ class SAC(EngineAgent):
 
     def _info_keys(self):
         if getattr(self, "_ext", {}).get("awac_lambda", 0.0) > 0:  # (the engine's offline programs)
-            return ("train/q_fn", "train/policy", "entropy", "train/adv", "train/weight")
-        if self.auto_tmp_mode:  # sac.py:268-290
-            return ("train/q_fn", "tmp", "norm/tmp", "train/policy", "train/tmp", "entropy")
-        return ("train/q_fn", "train/policy", "entropy")
+            keys = ("train/q_fn", "train/policy", "entropy", "train/adv", "train/weight")
+        elif self.auto_tmp_mode:  # sac.py:268-290
+            keys = ("train/q_fn", "tmp", "norm/tmp", "train/policy", "train/tmp", "entropy")
+        else:
+            keys = ("train/q_fn", "train/policy", "entropy")
+        return self._with_hops(keys)
 
     @property
     def tmp(self):

@@ -33,6 +33,12 @@ class TD3(EngineAgent):
     the critics ``Linear -> Dropout(p) -> LayerNorm -> activation``, the DroQ critic: inverted dropout as
     ``torch.nn.Dropout(p)`` in train mode, active in every critic pass of the device step (target, online, policy),
     drawn from a Philox stream of its own, and off in ``engine.eval_q`` (inference); the host copies carry it too.
+
+    ``n_step`` (keyword-only, default 1 = one-step targets, at most 8) trains on n-step returns: the device sampler
+    walks up to ``n_step`` consecutive rows of the sampled slot's episode (continuity is read from the data:
+    ``next_state[i] == state[i + 1]`` bit for bit) and the critic target becomes ``R_n + gamma^hops * notdone *
+    Q'(s_last')``; the info dict gains ``replay/hops``, the batch's mean hops.  ``replay.sample(B, n_step=n,
+    discount=gamma)`` returns the same rows on the host; a host BATCH dict is refused.
     """
 
     ALG = "td3"
@@ -48,7 +54,9 @@ class TD3(EngineAgent):
                  make_nn=None, *, hidden: int = 256, batch_size: int = 256, seed: int | None = None,
                  device=None, offline: bool = False, alpha: float = 2.5,
                  clip_grad_norm: float = float("inf"), critic_layer_norm: bool = False,
-                 critic_dropout: float = 0.0, **make_nn_kwargs) -> None:
+                 critic_dropout: float = 0.0, n_step: int = 1, **make_nn_kwargs) -> None:
+        # (n-step returns: the device sampler hands the step the n-step reward, next state and discount factor)
+        self._set_n_step(n_step)
         # (parameter-free LayerNorm after every hidden Linear of the critics and their targets, in the device step)
         self._set_layer_norm(critic_layer_norm)
         # (DroQ critics: dropout on every hidden Linear's output ahead of that LayerNorm, in the device step's passes)
@@ -74,7 +82,7 @@ class TD3(EngineAgent):
     def _info_keys(self):
         keys = ("train/q_fn", "train/policy", "norm/policy")  # td3.py:226-235
         bc = getattr(self, "_ext", {}).get("bc_alpha", 0.0) > 0  # (the engine's offline programs: two more columns)
-        return keys + ("train/bc", "train/lmbda") if bc else keys
+        return self._with_hops(keys + ("train/bc", "train/lmbda") if bc else keys)
 
     def sample(self, state, deterministic: bool = False, **kwargs):
         """td3.py:114-135: clip(tanh(policy(s)) + exploration_noise * randn, -1, 1) * scale + bias, one

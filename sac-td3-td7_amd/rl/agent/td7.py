@@ -38,7 +38,9 @@ class TD7(EngineAgent):
                  target_policy_noise: float = 0.2, noise_clip: float = 0.5, policy_freq: int = 2,
                  use_lap: bool = False, make_nn=None, *, hidden: int = 256, batch_size: int = 256,
                  seed: int | None = None, device=None, offline: bool = False, lmbda: float = 0.1,
-                 clip_grad_norm: float = float("inf"), **make_nn_kwargs) -> None:
+                 clip_grad_norm: float = float("inf"), n_step: int = 1, **make_nn_kwargs) -> None:
+        # (n_step > 1 raises: the encoder learns the one-step model zsa(s, a) -> zs(s') from the same next-state rows)
+        self._set_n_step(n_step)
         self._set_clip(clip_grad_norm)  # (global-norm clipping of the encoder's, critics' and policy's optimizer steps)
         self.discount_factor = discount_factor
         self.target_update_rate = target_update_rate

@@ -155,20 +155,31 @@ class BaseReplayMemory:
         return mean, scale
 
     # ---- sampling --------------------------------------------------------
-    def sample(self, batch_size: int, use_torch: bool = True):
+    def sample(self, batch_size: int, use_torch: bool = True, *, n_step: int = 1, discount: float = 0.99):
         """lap.py:45-64 / simple.py:45-62: u = torch.rand(B) from torch's global generator,
-        device index search, row gather."""
+        device index search, row gather.  ``n_step`` > 1: the n-step host batch of the sampled slots
+        (rle_replay_gather_nstep with ``discount``): reward holds the n-step return, next_state the last hop's, done
+        ``discount^(hops-1)`` times the last hop's not-done mask, and ``hops`` the rows' hop counts; ``ind`` stays
+        the sampled slots, which is what an ``n_step`` agent's ``train_ops`` recomputes the rows from."""
         import torch
 
+        n_step = E.check_n_step(-1, n_step)
         self.flush()
         u = torch.rand(batch_size).numpy()
         ind = self.dev.sample_indices(u)
-        s, a, r, s2, d = self.dev.gather(ind)
+        hops = None
+        if n_step > 1:
+            s, a, r, s2, d, hops = self.dev.gather_nstep(ind, n_step, discount)
+        else:
+            s, a, r, s2, d = self.dev.gather(ind)
         data = dict(state=s, action=a, reward=r[:, None], next_state=s2, done=d[:, None])
         if use_torch:
             data = {k: torch.from_numpy(v) for k, v in data.items()}
         self.ind = ind
-        return DeviceBatch(data, ind, self)
+        batch = DeviceBatch(data, ind, self)
+        if hops is not None:
+            batch.hops = hops
+        return batch
 
     # ---- save / restore / copy / move --------------------------------------
     # The reference's replays are NumPy arrays (lap.py:18-29, simple.py:15-27): pickle, deepcopy and a
